@@ -16,6 +16,12 @@ Multi-GPU: one process per GPU, sequences sharded per rank, no data-path collect
 shards sequences over a Pool, test_rgbt_mgpus.py:180-184); a gloo barrier and a max-over-ranks of the
 timed region only.  `--gpus N` without a torchrun environment spawns the N rank processes itself
 (before anything touches a GPU); under torchrun WORLD_SIZE must equal --gpus.
+
+A plain run sets up, warms up, times --steps steps and prints the result line.  `--full` adds every other
+measurement to that line: the one-sequence / OSTrack-384 / mfDiMP samples (`extra_workloads`), the PCIe-inclusive
+pass, the per-class timing probe behind `roofline`, and the CPU baseline.  `--dump-outputs DIR` writes what the
+last timed step returned to its caller (boxes, scores) as DIR/<name>.npy; weights, frames and start boxes are
+seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import collections
@@ -158,7 +164,8 @@ def run_extras(timeout=150):
     child's own JSON line reduced to its rate, step time and roofline fraction."""
     out = {}
     for name, argv in EXTRAS.items():
-        cmd = [sys.executable, os.path.abspath(__file__), "--no-extras", "--no-cpu-baseline", "--host-frames", "0"] + argv
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-extras", "--no-cpu-baseline", "--host-frames",
+               "0"] + argv
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
@@ -215,6 +222,20 @@ def aggregate_throughput(batch, steps, elapsed):
     _, world = rank_world()
     elapsed = max_over_ranks(elapsed)
     return world * batch * steps / elapsed, elapsed, world
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """What the last timed step handed its caller, one DIR/<name>.npy per array (float32 / float64); ranks past
+    the first of a multi-GPU run add their rank to the name."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 and rank else "") + ".npy"), a)
+    assert total <= 64 << 20, total
 
 
 def probe_classes(eng, step, k0, nsteps, precision):
@@ -292,7 +313,12 @@ def main():
     ap.add_argument("--dimp-precision", default="f16x3", choices=("f16x3", "fp32"),
                     help="mfdimp_rgbt: ResNet-50 convs on fp32-faithful f16x3 split products (default) or fp32 MFMA")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the one-sequence / OSTrack-384 / mfDiMP samples the default 1-GPU line carries")
+                    help="--full: skip the one-sequence / OSTrack-384 / mfDiMP samples the default 1-GPU line carries")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the extra workloads, the PCIe-inclusive "
+                         "pass, the per-class timing probe (roofline) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (boxes, scores) to DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -311,8 +337,8 @@ def main():
     if args.dry:
         return dry_main(args, rank, world, dist)
     extras = None
-    if (world == 1 and "WORLD_SIZE" not in os.environ and not args.no_extras and args.workload == "vipt_deep_rgbt"
-            and args.batch == 32 and args.precision == "fp32"):
+    if (args.full and world == 1 and "WORLD_SIZE" not in os.environ and not args.no_extras
+            and args.workload == "vipt_deep_rgbt" and args.batch == 32 and args.precision == "fp32"):
         extras = run_extras()   # children first: this process has not touched the GPU yet
     torch.cuda.set_device(local)
     if args.workload == DIMP_WORKLOAD:
@@ -336,23 +362,26 @@ def main():
     frame_lists = [[video[1 + t]] * B for t in range(args.frames)]
 
     def step(k, lists=frame_lists):
-        eng.track_batch(0, lists[k % args.frames])
+        return eng.track_batch(0, lists[k % args.frames])
 
     def run(k0, count, lists=frame_lists):
         """`count` frames of every sequence.  Pipelined (default): the tracker state lives on the device,
         so frame k+1 is submitted before frame k's boxes are fetched (at most LAG frames in flight);
-        every frame's boxes reach the host before this returns.  --sync: one blocking call per frame."""
+        every frame's boxes reach the host before this returns.  --sync: one blocking call per frame.
+        Returns the last frame's (boxes, scores)."""
+        last = None
         if args.sync:
             for k in range(k0, k0 + count):
-                step(k, lists)
-            return
+                last = step(k, lists)
+            return last
         pend = collections.deque()
         for k in range(k0, k0 + count):
             pend.append(eng.track_batch_submit(0, lists[k % args.frames]))
             if len(pend) > LAG:
-                eng.track_batch_fetch(pend.popleft())
+                last = eng.track_batch_fetch(pend.popleft())
         while pend:
-            eng.track_batch_fetch(pend.popleft())
+            last = eng.track_batch_fetch(pend.popleft())
+        return last
 
     run(0, max(args.warmup, 2))
     torch.cuda.synchronize()
@@ -360,17 +389,19 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run(args.warmup, args.steps)
+    last = run(args.warmup, args.steps)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     if dist:
         dist.barrier()
     value, elapsed, world = aggregate_throughput(B, args.steps, t1 - t0)
+    if args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, {"boxes": last[0], "scores": last[1]}, rank, world)
 
     # PCIe-inclusive rate: the same steps with every frame handed over as a host array in pinned memory
     # (the reference's per-frame call receives a host np.ndarray); copies run on the engine's copy stream
     host_fps = None
-    if args.host_frames > 0:
+    if args.full and args.host_frames > 0:
         pinned = [torch.from_numpy(video_np[1 + t]).pin_memory().numpy() for t in range(args.frames)]
         host_lists = [[pinned[t]] * B for t in range(args.frames)]
         run(0, 2, host_lists)
@@ -381,13 +412,13 @@ def main():
         host_fps = B * args.host_frames / (time.perf_counter() - th)
 
     roof = None
-    if args.probe and args.probe != "none":
+    if args.full and args.probe and args.probe != "none":
         classes = probe_classes(eng, step, args.warmup, min(args.steps, 10), args.precision)
         roof = roofline_from(classes, args.precision, args.workload, B)
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(args.workload, video_np, gts, args.cpu_seconds)
         gf = GFLOP_PER_FRAME[args.workload]
         line = {
@@ -448,62 +479,36 @@ def dimp_main(args, rank, world, dist):
         frame; default: PipelinedBatch over --dimp-groups groups of sequences -- with 2, the host updates of
         one group run under the other's network; 1, the whole batch per launch, is faster on MI355X since the
         grouped split-K convs want the larger M)."""
+        last = None
         for k in range(k0, k0 + n):
             frames = [video[1 + k % args.frames]] * B
             if pipe is None:
-                track_batch(trackers, frames)
+                last = track_batch(trackers, frames)
             else:
                 pipe.step(frames)
-        if pipe is not None:
-            pipe.flush()
+        if pipe is not None and n > 0:
+            last = pipe.flush()
+        return last
 
     run(0, max(args.warmup, 2))
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
     t0 = time.perf_counter()
-    run(args.warmup, args.steps)
+    last = run(args.warmup, args.steps)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     if dist:
         dist.barrier()
     value, elapsed, world = aggregate_throughput(B, args.steps, t1 - t0)
-    # roofline: the feature net (fp32 MFMA convs, >99 % of the step's FLOPs) timed with HIP events on the
-    # stream its kernels run on (torch's current stream)
-    patches = torch.rand(B, 6, 288, 288, device="cuda") * 255
-    net.extract_classification_feat(net.extract_backbone(patches))
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    reps = 5
-    ev0.record()
-    for _ in range(reps):
-        net.extract_classification_feat(net.extract_backbone(patches))
-    ev1.record()
-    torch.cuda.synchronize()
-    feat_ms = ev0.elapsed_time(ev1) / reps
-    flops = net.flops() * B
-    achieved = flops / (feat_ms * 1e-3) / 1e12
-    f16 = args.dimp_precision == "f16x3"
-    peak = PEAK_BF16_TFLOPS / 3 if f16 else PEAK_FP32_MATRIX_TFLOPS
-    tr = dimp_traffic(B) if f16 else None
-    roof = {"bound": "mfma", "kernel": ("f16x3 convs: conv_f16x3_deep_kernel, conv3x3_patch_f16x3_kernel, "
-                                        "conv_stem_pool_f16x3_kernel" if f16 else "conv_f32_kernel") +
-            " (2 x ResNet-50 to layer3 + clf conv, per batch)",
-            "achieved": round(achieved, 1), "peak": round(peak, 1), "unit": "TFLOP/s",
-            "frac": round(achieved / peak, 4), "traffic": None,
-            # no PMC pass runs inside bench.py: the committed summary's figure, named as such (ADVICE r4)
-            "traffic_committed": tr,
-            "traffic_unit": "bytes per 32-image feature-net batch (FETCH_SIZE x2 + WRITE_SIZE, PMC)",
-            "flop_per_launch_group": flops, "avg_batch_ms": round(feat_ms, 4),
-            # the feature net is partly HBM-bound (fp32 activations, 1x1 convs of K = 64..256): its per-layer
-            # roofline (sum over layers of max(FLOPs / peak, min bytes / 8 TB/s)) and the fraction of it reached
-            "layer_roofline_ms": round(net.roofline_ms(B, peak, PEAK_HBM_GBS / 1e3), 4),
-            "frac_of_layer_roofline": round(net.roofline_ms(B, peak, PEAK_HBM_GBS / 1e3) / feat_ms, 4),
-            "peak_note": ("f16x3 split products (Wh*Ah + Wl*Ah + Wh*Al, fp16 MFMA at the bf16 rate): dense 2500 TF/s / 3 "
-                          "of algorithmic FLOPs, fp32-faithful (the reference runs fp32)") if f16 else
-                         "dense fp32 matrix (v_mfma_f32_16x16x4_f32): the DiMP path runs at the reference's fp32"}
+    if args.dump_outputs and last is not None:
+        import numpy as np
+        dump_outputs(args.dump_outputs, {"boxes": np.array([o["target_bbox"] for o in last], np.float64),
+                                         "scores": np.array([o["confidence"] for o in last], np.float32)}, rank, world)
+    roof = dimp_roofline(args, net, B) if args.full else None
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import dimp as od
             from oracle import dimpnet as odn
             torch.set_num_threads(cpu_quota())
@@ -519,6 +524,7 @@ def dimp_main(args, rank, world, dist):
             cpu = {"value": round(n / dt, 3), "unit": "frames/s", "cores": cpu_quota(), "kind": "port",
                    "sample": f"{n} frames of the fp32 CPU oracle DiMP-50 feature net + classifier "
                              f"(oracle/dimpnet.py, {cpu_quota()} threads, {dt:.1f} s)"}
+        f16 = args.dimp_precision == "f16x3"
         line = {"metric": METRIC, "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
                 "scaling": "weak", "vs_baseline": None, "dtype": "f16x3" if f16 else "f32", "data": "synthetic",
@@ -533,6 +539,42 @@ def dimp_main(args, rank, world, dist):
         print(json.dumps(line), flush=True)
     if dist:
         dist.destroy_process_group()
+
+
+def dimp_roofline(args, net, B):
+    """--full: the mfDiMP feature net (fp32 MFMA convs, >99 % of the step's FLOPs) timed with HIP events on the
+    stream its kernels run on (torch's current stream)."""
+    patches = torch.rand(B, 6, 288, 288, device="cuda") * 255
+    net.extract_classification_feat(net.extract_backbone(patches))
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    reps = 5
+    ev0.record()
+    for _ in range(reps):
+        net.extract_classification_feat(net.extract_backbone(patches))
+    ev1.record()
+    torch.cuda.synchronize()
+    feat_ms = ev0.elapsed_time(ev1) / reps
+    flops = net.flops() * B
+    achieved = flops / (feat_ms * 1e-3) / 1e12
+    f16 = args.dimp_precision == "f16x3"
+    peak = PEAK_BF16_TFLOPS / 3 if f16 else PEAK_FP32_MATRIX_TFLOPS
+    tr = dimp_traffic(B) if f16 else None
+    return {"bound": "mfma", "kernel": ("f16x3 convs: conv_f16x3_deep_kernel, conv3x3_patch_f16x3_kernel, "
+                                        "conv_stem_pool_f16x3_kernel" if f16 else "conv_f32_kernel") +
+            " (2 x ResNet-50 to layer3 + clf conv, per batch)",
+            "achieved": round(achieved, 1), "peak": round(peak, 1), "unit": "TFLOP/s",
+            "frac": round(achieved / peak, 4), "traffic": None,
+            # no PMC pass runs inside bench.py: the committed summary's figure, named as such (ADVICE r4)
+            "traffic_committed": tr,
+            "traffic_unit": "bytes per 32-image feature-net batch (FETCH_SIZE x2 + WRITE_SIZE, PMC)",
+            "flop_per_launch_group": flops, "avg_batch_ms": round(feat_ms, 4),
+            # the feature net is partly HBM-bound (fp32 activations, 1x1 convs of K = 64..256): its per-layer
+            # roofline (sum over layers of max(FLOPs / peak, min bytes / 8 TB/s)) and the fraction of it reached
+            "layer_roofline_ms": round(net.roofline_ms(B, peak, PEAK_HBM_GBS / 1e3), 4),
+            "frac_of_layer_roofline": round(net.roofline_ms(B, peak, PEAK_HBM_GBS / 1e3) / feat_ms, 4),
+            "peak_note": ("f16x3 split products (Wh*Ah + Wl*Ah + Wh*Al, fp16 MFMA at the bf16 rate): dense 2500 TF/s / 3 "
+                          "of algorithmic FLOPs, fp32-faithful (the reference runs fp32)") if f16 else
+                         "dense fp32 matrix (v_mfma_f32_16x16x4_f32): the DiMP path runs at the reference's fp32"}
 
 
 def dry_main(args, rank, world, dist):
