@@ -52,6 +52,7 @@ enum {
 
 enum { MMT_MODEL_VIPT = 0, MMT_MODEL_OSTRACK = 1 };
 enum { MMT_PROMPT_NONE = 0, MMT_PROMPT_SHAW = 1, MMT_PROMPT_DEEP = 2 };
+#define MMT_CE_TEMPLATE_MASK (-2)   /* mmt_config.ce_template_index: mask mode */
 
 typedef struct mmt_config {
   int model;               /* MMT_MODEL_*                                           */
@@ -64,7 +65,9 @@ typedef struct mmt_config {
   int n_ce;                /* len(cfg.MODEL.BACKBONE.CE_LOC)                        */
   int ce_loc[12];
   double ce_keep_ratio[12];
-  int ce_template_index;   /* CTR_POINT template token (generate_mask_cond, ce_utils.py:22-35) */
+  int ce_template_index;   /* >= 0: the CTR_POINT template token (generate_mask_cond, ce_utils.py:22-35);
+                              MMT_CE_TEMPLATE_MASK: a per-slot set of template tokens (ALL / CTR_REC / GT_BOX,
+                              ce_utils.py:20, 36-59), all tokens until mmt_set_ce_template_mask says otherwise */
   int head_channels;       /* cfg.MODEL.HEAD.NUM_CHANNELS (256)                     */
   int max_batch;           /* sequences (slots) this engine tracks concurrently    */
   int use_graphs;          /* capture the per-frame launch sequence in a hipGraph   */
@@ -84,8 +87,9 @@ const char* mmt_version(void);
 /* ABI revision of this header; a binding checks it once at load.  5: the strided DiMP optimiser is
  * mmt_dimp_optimize_strided (-1 = contiguous stride, 0 = broadcast; the round-3 entry point
  * mmt_dimp_optimize_dev, where 0 meant contiguous, is gone, so an old binding fails to resolve it
- * instead of silently reading sample 0 everywhere). */
-#define MMT_ABI_VERSION 5
+ * instead of silently reading sample 0 everywhere).  6: candidate elimination over any template mask
+ * (MMT_CE_TEMPLATE_MASK, mmt_set_ce_template_mask, mmt_op_ce_rows / _f16x3, timing class "ce_rows"). */
+#define MMT_ABI_VERSION 6
 int mmt_abi_version(void);
 /* pinned host memory that kernels read and write in place (mapped + coherent: a kernel sees the host's latest
  * writes and the host sees the kernel's after an event, with no copy launch) -- the DiMP pool's frame descriptors
@@ -114,6 +118,12 @@ int mmt_get_state(const mmt_engine* e, int slot, double out_xywh[4]);
  * legacy default stream).  Without this call device frames must be complete when they are passed. */
 int mmt_set_frame_stream(mmt_engine* e, void* hip_stream);
 int mmt_set_state(mmt_engine* e, int slot, const double xywh[4]);
+/* mask mode (cfg.ce_template_index = MMT_CE_TEMPLATE_MASK): the template tokens whose attention rows score the
+ * search tokens of `slot` (box_mask_z of generate_mask_cond, ce_utils.py:15-65; the score is the mean over the set,
+ * then over heads, attn_blocks.py:44-53).  mask: n = Lz bytes, non-zero = in the set; slot = -1: every slot.  A mask
+ * with no token set is MMT_E_ARG, an engine not in mask mode MMT_E_STATE.  Stream-ordered on the engine stream like
+ * mmt_set_state; captured graphs stay valid (the kernel reads the lists from fixed device addresses).      */
+int mmt_set_ce_template_mask(mmt_engine* e, int slot, const uint8_t* mask, int n);
 
 /* pipelined tracking.  The tracker state machine of ViPTTrack.track (crop geometry from the last box,
  * processing_utils.py:32-41; box back-map + clip_box, vipt.py:84-88, box_ops.py:97-106) runs on the
@@ -133,7 +143,8 @@ int mmt_track_batch_fetch(mmt_engine* e, int64_t ticket, double* out_xywh, float
  *   "crop"   uint8 [S][S][C]  search patch         "maps"  f32 [5][fs*fs] ctr,size_w,size_h,off_x,off_y
  *   "feat"   f32 [Lz+Lx][768] backbone output      "removed" i32 [Lx] removed slots, CE order
  *   "result" f32 [8] cx,cy,w,h (normalised), best_score, argmax index
- *   "ce_keys" f32 [n_ce][Lx] CE score (head mean of the CTR_POINT row, attn_blocks.py:44-53) of every
+ *   "ce_keys" f32 [n_ce][Lx] CE score (head mean of the template mask's rows -- the CTR_POINT row, or the
+ *            mean over the slot's mask in mask mode --, attn_blocks.py:44-53) of every
  *            slot that entered each CE stage, by slot id                                        */
 int mmt_debug_fetch(mmt_engine* e, const char* what, int batch_index, void* dst, size_t nbytes);
 /* teacher-forced candidate elimination (parity diagnosis, debug_outputs = 1): keys [n_ce][Lx] by slot id
@@ -143,7 +154,8 @@ int mmt_debug_fetch(mmt_engine* e, const char* what, int batch_index, void* dst,
 int mmt_debug_force_ce(mmt_engine* e, int slot, const float* keys, size_t n_floats);
 
 /* kernel timing probe: bracket every launch of one kernel class with HIP events on the engine
- * stream ("fc1", "fc2", "qkv", "proj", "attn", "conv1"); returns launches and summed ms */
+ * stream ("fc1", "fc2", "qkv", "proj", "attn", "conv1", "ce_rows": the mask mode's CE probability kernel);
+ * returns launches and summed ms */
 int mmt_timing_enable(mmt_engine* e, const char* kernel_class);
 int mmt_timing_read(mmt_engine* e, int* launches, double* total_ms, double* flops, double* bytes);
 
@@ -423,7 +435,9 @@ int mmt_op_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, const fl
                 const float* R, int64_t ldr, int M, int N, int K, int epi, int conv_hw, int conv_cin, int pos_rows,
                 void* hip_stream);
 int mmt_gemm_force_config(int cfg);   /* tuning: pin the dense-GEMM tile config (-1 = heuristic); 320 / 256 pin the
-                                         f16x3 qkv / fc1 GEMMs to 320 x 256 / 256 x 256 tiles */
+                                         f16x3 qkv / fc1 GEMMs to 320 x 256 / 256 x 256 tiles (320 applies to the
+                                         bf16 and GELU-bf16 epilogues only, any other epilogue takes 256 x 256);
+                                         128 pins the 128 x 256 tile of the fp32-output epilogues */
 int mmt_gemm_stamps(void* dev_buf);   /* tuning: per-block s_memtime stamps [blocks][4] (start, main loop,
                                          epilogue, end) into a device buffer; NULL turns them off */
 int mmt_op_attention(const void* qkv, void* out, int B, int N, int heads, int ce_query, int ce_lens_t,
@@ -440,6 +454,14 @@ int mmt_op_gemm_f16x3(const void* A_hi, const void* A_lo, int64_t lda, const voi
                       int epi, float inv, float out_scale, int conv_hw, int conv_cin, void* hip_stream);
 int mmt_op_attention_f16x3(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, int B, int N, int heads,
                            int ce_query, int ce_lens_t, float* ce_prob, float s_qkv, void* hip_stream);
+/* the mask mode's CE kernel (csrc/ce_rows.hip) on the qkv buffer attention reads: ce_prob [B][heads][N - lens_t] =
+ * the mean over the sequence's template rows of their softmax probabilities at the search keys.  rows: device
+ * [B][rows_pitch] ascending row indices < lens_t, nrows: device [B], 1 <= nrows[b] <= min(lens_t, rows_pitch);
+ * lens_t < N.  The lists are read back and checked before the launch (MMT_E_ARG, nothing launched).        */
+int mmt_op_ce_rows(const void* qkv, int B, int N, int heads, int lens_t, const int* rows, int rows_pitch,
+                   const int* nrows, float* ce_prob, void* hip_stream);
+int mmt_op_ce_rows_f16x3(const void* qkv_hi, const void* qkv_lo, int B, int N, int heads, int lens_t, const int* rows,
+                         int rows_pitch, const int* nrows, float* ce_prob, float s_qkv, void* hip_stream);
 
 #ifdef __cplusplus
 }

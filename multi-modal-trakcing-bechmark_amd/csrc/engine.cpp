@@ -134,6 +134,11 @@ struct mmt_engine {
         *c8 = nullptr, *fstat = nullptr, *h4 = nullptr, *ce_prob = nullptr, *res = nullptr, *dbg_maps = nullptr,
         *dbg_feat = nullptr;
   int *gidx0 = nullptr, *gidx1 = nullptr, *slot2pos = nullptr, *gather = nullptr, *removed = nullptr;
+  // mask mode (cfg.ce_template_index = MMT_CE_TEMPLATE_MASK): per slot, the compact ascending list of the template
+  // tokens whose attention rows score the search tokens ([max_batch][Lz]) and its length; every token (ALL) until
+  // mmt_set_ce_template_mask.  Fixed device addresses: captured graphs read the lists' current contents.
+  bool ce_mask = false;
+  int *ce_rows = nullptr, *ce_nrows = nullptr;
   float* splitk_ws = nullptr;   // [kMaxParts launch parts][kSplitKWsElems] fp32 split-K partials (few-tile GEMMs)
   uint8_t* dbg_patch = nullptr;
   CropParam* params_dev = nullptr;
@@ -572,6 +577,10 @@ int alloc_acts(mmt_engine* e) {
       {(void**)&e->state_dev, (size_t)B * sizeof(SeqState)}, {(void**)&e->out_dev, (size_t)B * sizeof(TrackOut)},
   };
   reqs.push_back({(void**)&e->zero, 256});
+  if (e->ce_mask) {
+    reqs.push_back({(void**)&e->ce_rows, (size_t)B * e->Lz * 4});
+    reqs.push_back({(void**)&e->ce_nrows, (size_t)B * 4});
+  }
   reqs.push_back({(void**)&e->hring.ctr, 256});   // ctr, cur
   reqs.push_back({(void**)&e->splitk_ws, (size_t)mmt_engine::kMaxParts * kSplitKWsElems * 4});
   if (e->split) {
@@ -599,6 +608,12 @@ int alloc_acts(mmt_engine* e) {
   for (auto& r : reqs) {
     *r.p = static_cast<char*>(e->aarena) + off;
     off += (r.bytes + 255) & ~size_t(255);
+  }
+  if (e->ce_mask) {   // ALL: every template token of every slot
+    std::vector<int> rows((size_t)B * e->Lz), nrows(B, e->Lz);
+    for (size_t i = 0; i < rows.size(); ++i) rows[i] = (int)(i % e->Lz);
+    HIPCHECK(e, hipMemcpy(e->ce_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+    HIPCHECK(e, hipMemcpy(e->ce_nrows, nrows.data(), nrows.size() * 4, hipMemcpyHostToDevice));
   }
   // the ring is read / written by kernels in place: fine-grained coherent pinned memory, so no GPU cache
   // holds a stale copy of an entry between the launches that reuse it (frame pointer / size may change)
@@ -929,7 +944,7 @@ void enqueue_forward(mmt_engine* e, int b0, int r0, int n, hipStream_t s, int pa
     aa.B = n;
     aa.N = Na;
     aa.heads = HEADS;
-    aa.ce_query = ce ? c.ce_template_index : -1;
+    aa.ce_query = ce && !e->ce_mask ? c.ce_template_index : -1;
     aa.ce_lens_t = Lz;
     aa.ce_prob = q_ce_prob;
     // algorithmic bytes: Q, K, V in and O out, 2 B per element, twice in the parity mode (hi + lo planes: 12 288 B per
@@ -937,6 +952,25 @@ void enqueue_forward(mmt_engine* e, int b0, int r0, int n, hipStream_t s, int pa
     probe_begin(e, s, "attn", 4.0 * n * HEADS * (double)Na * Na * 64, (double)n * Na * 4 * C * 2 * (e->split ? 2 : 1));
     attention(aa, s);
     probe_end(e, s, "attn");
+    if (ce && e->ce_mask) {   // the mean over the slots' template masks instead of attention's single exported row
+      CeRowsArgs cr{};
+      cr.qkv = q_QKV;
+      cr.qkv_lo = q_QKV_l;
+      cr.B = n;
+      cr.N = Na;
+      cr.heads = HEADS;
+      cr.lens_t = Lz;
+      cr.rows = e->ce_rows + (size_t)b0 * Lz;
+      cr.pitch = Lz;
+      cr.nrows = e->ce_nrows + b0;
+      cr.prob = q_ce_prob;
+      cr.qk_inv = aa.qk_inv;
+      // at most Lz rows against Na keys, twice (the search-key tiles are multiplied again): K of every head once
+      probe_begin(e, s, "ce_rows", 2.0 * n * HEADS * (double)Lz * (2.0 * Na - Lz) * 64,
+                  (double)n * Na * C * 2 * (e->split ? 2 : 1));
+      ce_rows(cr, s);
+      probe_end(e, s, "ce_rows");
+    }
     pend = run_resid_gemm(
         e, s, "proj",
         scaled(dense(e, q_ws, q_O, q_O_l, C, w.proj_w, w.proj_wl, C, w.proj_b, X, nullptr, C, X, C, n * Na, C, C),
@@ -1233,7 +1267,9 @@ int mmt_create(const mmt_config* cfg, int device, mmt_engine** out) {
   e->L = e->Lz + e->Lx;
   e->fs = c.search_size / 16;
   e->tfs = c.template_size / 16;
-  if (e->L > 1024 || (c.n_ce > 0 && (c.ce_template_index < 0 || c.ce_template_index >= e->Lz))) return MMT_E_ARG;
+  e->ce_mask = c.ce_template_index == MMT_CE_TEMPLATE_MASK;
+  if (e->L > 1024 || (c.n_ce > 0 && !e->ce_mask && (c.ce_template_index < 0 || c.ce_template_index >= e->Lz)))
+    return MMT_E_ARG;
   if (c.precision < 0 || c.precision > 1) return MMT_E_ARG;
   e->split = c.precision == 1;
   e->nprompt = c.model == MMT_MODEL_VIPT ? (c.prompt_type == MMT_PROMPT_DEEP ? DEPTH : (c.prompt_type ? 1 : 0)) : 0;
@@ -1528,6 +1564,28 @@ int mmt_set_state(mmt_engine* e, int slot, const double xywh[4]) {
   return write_state(e, slot);
 }
 
+int mmt_set_ce_template_mask(mmt_engine* e, int slot, const uint8_t* mask, int n) {
+  int r = check_engine(e);
+  if (r) return r;
+  if (!e->ce_mask) return e->fail(MMT_E_STATE, "engine not in mask mode (ce_template_index = MMT_CE_TEMPLATE_MASK)");
+  if (!mask || n != e->Lz || slot < -1 || slot >= e->cfg.max_batch)
+    return e->fail(MMT_E_ARG, "bad CE template mask (expect Lz bytes, slot in [-1, max_batch))");
+  if (e->unfetched) return e->fail(MMT_E_STATE, "set_ce_template_mask with unfetched frames in flight");
+  std::vector<int> rows(e->Lz, 0);
+  int nr = 0;
+  for (int i = 0; i < n; ++i)
+    if (mask[i]) rows[nr++] = i;
+  if (nr == 0) return e->fail(MMT_E_ARG, "CE template mask selects no token");
+  // stream-ordered after the frames enqueued so far, synchronous (the host vectors die here), as write_state
+  for (int sl = slot < 0 ? 0 : slot; sl < (slot < 0 ? e->cfg.max_batch : slot + 1); ++sl) {
+    HIPCHECK(e, hipMemcpyAsync(e->ce_rows + (size_t)sl * e->Lz, rows.data(), (size_t)e->Lz * 4, hipMemcpyHostToDevice,
+                               e->stream));
+    HIPCHECK(e, hipMemcpyAsync(e->ce_nrows + sl, &nr, 4, hipMemcpyHostToDevice, e->stream));
+  }
+  HIPCHECK(e, hipStreamSynchronize(e->stream));
+  return MMT_OK;
+}
+
 int mmt_debug_fetch(mmt_engine* e, const char* what, int bi, void* dst, size_t nbytes) {
   int r = check_engine(e);
   if (r) return r;
@@ -1781,6 +1839,67 @@ int mmt_op_attention_f16x3(const void* qkv_hi, const void* qkv_lo, void* out_hi,
   a.pv_inv = 1.0f / (16384.0f * s_qkv);
   a.out_scale = s_qkv;
   attention(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+namespace {
+// the lists of an operator-level ce_rows call, read back and checked (tests and composing hosts: synchronous)
+int check_ce_rows(int B, int N, int heads, int lens_t, const int* rows, int pitch, const int* nrows, const float* prob) {
+  if (B <= 0 || N <= 0 || N > 1024 || heads <= 0 || lens_t <= 0 || lens_t >= N || !rows || !nrows || !prob || pitch <= 0)
+    return MMT_E_ARG;
+  std::vector<int> hn(B), hr((size_t)B * pitch);
+  if (hipMemcpy(hn.data(), nrows, (size_t)B * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(hr.data(), rows, hr.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return MMT_E_HIP;
+  for (int b = 0; b < B; ++b) {
+    if (hn[b] < 1 || hn[b] > lens_t || hn[b] > pitch) return MMT_E_ARG;
+    for (int i = 0; i < hn[b]; ++i) {
+      const int r = hr[(size_t)b * pitch + i];
+      if (r < 0 || r >= lens_t || (i > 0 && r <= hr[(size_t)b * pitch + i - 1])) return MMT_E_ARG;
+    }
+  }
+  return MMT_OK;
+}
+}  // namespace
+
+int mmt_op_ce_rows_f16x3(const void* qkv_hi, const void* qkv_lo, int B, int N, int heads, int lens_t, const int* rows,
+                         int rows_pitch, const int* nrows, float* ce_prob, float s_qkv, void* stream) {
+  if (!qkv_hi || !qkv_lo || !(s_qkv > 0)) return MMT_E_ARG;
+  const int r = check_ce_rows(B, N, heads, lens_t, rows, rows_pitch, nrows, ce_prob);
+  if (r) return r;
+  CeRowsArgs a{};
+  a.qkv = (const bf16_t*)qkv_hi;
+  a.qkv_lo = (const bf16_t*)qkv_lo;
+  a.B = B;
+  a.N = N;
+  a.heads = heads;
+  a.lens_t = lens_t;
+  a.rows = rows;
+  a.pitch = rows_pitch;
+  a.nrows = nrows;
+  a.prob = ce_prob;
+  a.qk_inv = 0.125f / (s_qkv * s_qkv);   // mmt_op_attention_f16x3's
+  ce_rows(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_ce_rows(const void* qkv, int B, int N, int heads, int lens_t, const int* rows, int rows_pitch,
+                   const int* nrows, float* ce_prob, void* stream) {
+  if (!qkv) return MMT_E_ARG;
+  const int r = check_ce_rows(B, N, heads, lens_t, rows, rows_pitch, nrows, ce_prob);
+  if (r) return r;
+  CeRowsArgs a{};
+  a.qkv = (const bf16_t*)qkv;
+  a.qkv_lo = nullptr;
+  a.B = B;
+  a.N = N;
+  a.heads = heads;
+  a.lens_t = lens_t;
+  a.rows = rows;
+  a.pitch = rows_pitch;
+  a.nrows = nrows;
+  a.prob = ce_prob;
+  ce_rows(a, (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
 }
 

@@ -83,6 +83,22 @@ struct AttnArgs {
 };
 void attention(const AttnArgs& a, hipStream_t s);
 
+// CE probabilities averaged over a per-sequence set of template rows (ce_rows.hip), from the qkv buffer attention
+// read: prob[b][h][j] = 1 / nrows[b] * sum_{r in rows[b]} softmax_k(q_r . k_k * 64^-0.5)[lens_t + j], the layout of
+// AttnArgs::ce_prob.  rows: [B][pitch] ascending template row indices (device), nrows: [B], 1 <= nrows[b] <=
+// min(lens_t, pitch); lens_t < N <= 1024.
+struct CeRowsArgs {
+  const bf16_t* qkv;     // [B][N][3*C]
+  const bf16_t* qkv_lo;  // split mode: low halves (else null)
+  int B, N, heads, lens_t;
+  const int* rows;
+  int pitch;
+  const int* nrows;
+  float* prob;           // [B][heads][N - lens_t]
+  float qk_inv = 1.0f;   // split mode: AttnArgs::qk_inv
+};
+void ce_rows(const CeRowsArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------- layer norm (row of 768)
 // out_bf16[r] = LN(x[src(r)]), src(r) = gather ? b*in_pitch + gather[b][t] : r ; optional copy of x[src] to xcopy[r]
 // out_lo non-null: out_bf16 / out_lo are the f16x3 halves of LN * out_scale instead (common.h)
@@ -145,8 +161,6 @@ struct LnPromptArgs {
 // the fovea statistics of the row's sequence, s8 of its slot, the prompt residual (conv1x1 of s8, formed per
 // row from an LDS copy of conv1x1) and LN1, for the compact rows
 void prompt_expand_ln(const LnPromptArgs& a, hipStream_t s);
-// a deep layer's prompt_reduce (pa) and prompt_expand_ln (la, mode 2) as one launch whose blocks meet at a
-// per-sequence barrier (bar: [B][32] ints, zero at allocation, left zero); false: not taken (the caller launches the two)
 
 // ---------------------------------------------------------------- candidate elimination
 struct CEArgs {

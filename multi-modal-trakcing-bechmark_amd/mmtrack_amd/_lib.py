@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("MMTRACK_LIB", os.path.join(_HERE, "libmmtrack.so"))
 MMT_OK, MMT_E_ARG, MMT_E_STATE, MMT_E_HIP, MMT_E_WEIGHTS, MMT_E_BOX = 0, -1, -2, -3, -4, -5
 MMT_MODEL_VIPT, MMT_MODEL_OSTRACK = 0, 1
 MMT_PROMPT_NONE, MMT_PROMPT_SHAW, MMT_PROMPT_DEEP = 0, 1, 2
+MMT_CE_TEMPLATE_MASK = -2   # mmt_config.ce_template_index: a per-slot template mask instead of one token
 
 
 class MmtConfig(ctypes.Structure):
@@ -115,7 +116,7 @@ class MmtDimpResult(ctypes.Structure):
                 ("aux", ctypes.c_int * 4)]
 
 
-ABI_VERSION = 5   # include/mmtrack.h MMT_ABI_VERSION
+ABI_VERSION = 6   # include/mmtrack.h MMT_ABI_VERSION
 
 # every symbol include/mmtrack.h declares: name -> (restype, argtypes)
 _P = ctypes.c_void_p
@@ -142,6 +143,7 @@ SIGNATURES = {
     "mmt_track_batch_fetch": (_I, [_P, _I64, ctypes.POINTER(_D), ctypes.POINTER(_F)]),
     "mmt_get_state": (_I, [_P, _I, ctypes.POINTER(_D)]),
     "mmt_set_state": (_I, [_P, _I, ctypes.POINTER(_D)]),
+    "mmt_set_ce_template_mask": (_I, [_P, _I, _P, _I]),
     "mmt_debug_fetch": (_I, [_P, ctypes.c_char_p, _I, _P, ctypes.c_size_t]),
     "mmt_debug_force_ce": (_I, [_P, _I, _P, ctypes.c_size_t]),
     "mmt_timing_enable": (_I, [_P, ctypes.c_char_p]),
@@ -198,6 +200,8 @@ SIGNATURES = {
     "mmt_op_gemm_f16x3": (_I, [_P, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I, _I, _I, _I, _F, _F, _I, _I,
                                _P]),
     "mmt_op_attention_f16x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _F, _P]),
+    "mmt_op_ce_rows": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
+    "mmt_op_ce_rows_f16x3": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _F, _P]),
 }
 
 _lib = None

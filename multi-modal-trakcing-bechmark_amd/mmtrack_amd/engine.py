@@ -20,6 +20,9 @@ class TrackerError(Exception):
     pass
 
 
+CE_TEMPLATE_RANGES = ("CTR_POINT", "ALL", "CTR_REC", "GT_BOX", "MASK")
+
+
 @dataclass
 class EngineConfig:
     model: str = "vipt"               # "vipt" | "ostrack"
@@ -31,6 +34,9 @@ class EngineConfig:
     search_factor: float = 4.0
     ce_loc: List[int] = field(default_factory=lambda: [3, 6, 9])
     ce_keep_ratio: List[float] = field(default_factory=lambda: [0.7, 0.7, 0.7])
+    # cfg.MODEL.BACKBONE.CE_TEMPLATE_RANGE: "CTR_POINT" (one template token, exported by attention itself), "ALL" /
+    # "CTR_REC" / "GT_BOX" (a template mask per slot, set at initialize: the engine's mask mode), or "MASK" (mask
+    # mode with the caller's own masks, Engine.set_ce_template_mask; every token until then)
     ce_template_range: str = "CTR_POINT"
     head_channels: int = 256
     max_batch: int = 1
@@ -51,6 +57,11 @@ class EngineConfig:
                    ce_template_range=cfg.MODEL.BACKBONE.CE_TEMPLATE_RANGE,
                    head_channels=cfg.MODEL.HEAD.NUM_CHANNELS, **kw)
 
+    @property
+    def mask_mode(self) -> bool:
+        """The engine scores search tokens by a per-slot set of template tokens (every range but CTR_POINT)."""
+        return bool(self.ce_loc) and self.ce_template_range != "CTR_POINT"
+
     def ctr_point_index(self) -> int:
         """generate_mask_cond CTR_POINT (ViPT/lib/utils/ce_utils.py:22-35)."""
         tf = self.template_size // 16
@@ -69,13 +80,16 @@ class EngineConfig:
         c.search_size = self.search_size
         c.template_factor = self.template_factor
         c.search_factor = self.search_factor
-        if self.ce_loc and self.ce_template_range != "CTR_POINT":
-            raise NotImplementedError("only CE_TEMPLATE_RANGE = CTR_POINT is supported")
+        if self.ce_template_range not in CE_TEMPLATE_RANGES:
+            raise ValueError(f"ce_template_range must be one of {CE_TEMPLATE_RANGES}, got {self.ce_template_range!r}")
         c.n_ce = len(self.ce_loc)
         for i, (loc, r) in enumerate(zip(self.ce_loc, self.ce_keep_ratio)):
             c.ce_loc[i] = int(loc)
             c.ce_keep_ratio[i] = float(r)
-        c.ce_template_index = self.ctr_point_index() if self.ce_loc else -1
+        if self.mask_mode:
+            c.ce_template_index = L.MMT_CE_TEMPLATE_MASK
+        else:
+            c.ce_template_index = self.ctr_point_index() if self.ce_loc else -1
         c.head_channels = self.head_channels
         c.max_batch = self.max_batch
         c.use_graphs = int(self.use_graphs)
@@ -167,7 +181,40 @@ class Engine:
         keep, ptr, H, W, C, stride, dev = _frame_arg(image)
         self._order_device_frames(dev)
         b = (ctypes.c_double * 4)(*[float(v) for v in box])
+        mask = self._range_mask(box)
         self._check(self.lib.mmt_initialize(self.h, slot, ptr, H, W, C, stride, dev, b))
+        if mask is not None:
+            self.set_ce_template_mask(slot, mask)
+
+    # -- candidate elimination over a template mask (mask mode)
+    def _range_mask(self, box):
+        """The slot's template mask for cfg.ce_template_range, as ViPTTrack.initialize forms box_mask_z
+        (vipt.py:50-54): bool [Lz], or None when there is nothing to set (CTR_POINT, MASK, no CE layers)."""
+        cfg = self.cfg
+        if not cfg.mask_mode or cfg.ce_template_range == "MASK":
+            return None
+        from lib.utils import ce_utils
+        tf = cfg.template_size // 16
+        if cfg.ce_template_range == "ALL":
+            return np.ones(tf * tf, dtype=bool)
+        gt = None
+        if cfg.ce_template_range == "GT_BOX":
+            x, y, w, h = box if isinstance(box, list) else np.asarray(box).tolist()
+            crop_sz = math.ceil(math.sqrt(w * h) * cfg.template_factor)   # sample_target, processing_utils.py:32-35
+            if crop_sz < 1:
+                return None   # mmt_initialize raises "Too small bounding box."
+            gt = ce_utils.template_box_in_crop(box, cfg.template_size / crop_sz, cfg.template_size)
+        m = ce_utils.template_mask(cfg.ce_template_range, cfg.template_size, 16, 1, "cpu", gt)[0].numpy()
+        if not m.any():
+            # the reference averages an empty set there (NaN scores, an arbitrary kept set); refused instead
+            raise ValueError(f"GT_BOX template mask of init box {list(box)} selects no template token")
+        return m
+
+    def set_ce_template_mask(self, slot: int, mask):
+        """The template tokens whose attention rows score the search tokens of `slot` (-1: every slot): bool [Lz]
+        (or [tf, tf]), at least one set.  Takes effect from the next tracked frame, captured graphs included."""
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        self._check(self.lib.mmt_set_ce_template_mask(self.h, slot, m.ctypes.data, m.size))
 
     def track(self, slot: int, image):
         keep, ptr, H, W, C, stride, dev = _frame_arg(image)
