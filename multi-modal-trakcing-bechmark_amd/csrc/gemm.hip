@@ -1038,6 +1038,22 @@ static int num_cus() {
   return n;
 }
 
+// The launchers below only launch: which one runs, and the a.gm / a.ksplit it runs with, is gemm_plan's decision
+// (gemm_plan.cpp), which also holds every guard on what a kernel family can run.
+// with_epi<MASK>(epi, f): f(std::integral_constant<int, EPI>) for the run-time epilogue, instantiated for the
+// epilogues of MASK only (the family has no kernel for the others, and the planner never sends them)
+constexpr unsigned kEpi16 = 1u << EPI_BF16 | 1u << EPI_GELU_BF16, kEpiF32 = 1u << EPI_RESID_F32 | 1u << EPI_F32 | 1u << EPI_POS_F32,
+                   kEpiDense = kEpi16 | kEpiF32, kEpiRelu = 1u << EPI_RELU_BF16 | 1u << EPI_RELU_F32, kEpiAll = kEpiDense | kEpiRelu;
+template <unsigned MASK, int E = 0, class F>
+static void with_epi(int epi, F&& f) {
+  if constexpr (E <= EPI_POS_F32) {
+    if constexpr ((MASK >> E & 1) != 0)
+      if (epi == E) return f(std::integral_constant<int, E>{});
+    with_epi<MASK, E + 1>(epi, f);
+  }
+}
+#define EPI_OF(e) decltype(e)::value
+
 // ---------------------------------------------------------------------------------------------------
 // 256 x 256 tile, 8 waves (2 x 4), four phases per 64-deep K-tile (one 128 x 128 C quadrant per
 // phase; each wave owns a 64 x 32 piece of every quadrant).
@@ -1234,23 +1250,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs args) {
 }
 
 template <int EPI>
-static void launch256(const GemmArgs& a0, hipStream_t s) {
-  GemmArgs a = a0;
-  const int tiles_m = (a.M + 255) / 256;
-  a.gm = tiles_m < 4 ? tiles_m : 4;
-  dim3 grid(tiles_m * (a.N / 256), 1, a.groups);
+static void launch256(const GemmArgs& a, hipStream_t s) {
+  dim3 grid((a.M + 255) / 256 * (a.N / 256), 1, a.groups);
   hipLaunchKernelGGL(gemm256_kernel<EPI>, grid, dim3(512), 0, s, a);
-}
-
-static void launch256_epi(const GemmArgs& a, int epi, hipStream_t s) {
-  switch (epi) {
-    case EPI_BF16: return launch256<EPI_BF16>(a, s);
-    case EPI_GELU_BF16: return launch256<EPI_GELU_BF16>(a, s);
-    case EPI_RESID_F32: return launch256<EPI_RESID_F32>(a, s);
-    case EPI_F32: return launch256<EPI_F32>(a, s);
-    case EPI_POS_F32: return launch256<EPI_POS_F32>(a, s);
-    default: break;
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1677,32 +1679,9 @@ __global__ __launch_bounds__(512) void gemm256s_kernel(const GemmArgs args) {
 #undef PSTAMP
 
 template <int EPI, int MI>
-static void launch256s(const GemmArgs& a0, hipStream_t s) {
-  GemmArgs a = a0;
+static void launch256s(const GemmArgs& a, hipStream_t s) {
   const int tiles_m = (a.M + 64 * MI - 1) / (64 * MI);
-  static const int gm256 = getenv("MMT_GM256") ? atoi(getenv("MMT_GM256")) : 4;   // tuning: super-tile height
-  a.gm = tiles_m < gm256 ? tiles_m : gm256;
   hipLaunchKernelGGL((gemm256s_kernel<EPI, MI>), dim3(tiles_m * (a.N / 256), 1, a.groups), dim3(512), 0, s, a);
-}
-
-// t320: the 320 x 256 tiles (16-bit epilogues; false if the epilogue has none)
-static bool launch256s_epi(const GemmArgs& a, int epi, hipStream_t s, bool t320 = false) {
-  if (a.N % 256 || a.K % 32 || a.K < 64 || a.amode != A_DENSE) return false;
-  if (t320) {
-    switch (epi) {
-      case EPI_BF16: return launch256s<EPI_BF16, 5>(a, s), true;
-      case EPI_GELU_BF16: return launch256s<EPI_GELU_BF16, 5>(a, s), true;
-      default: return false;
-    }
-  }
-  switch (epi) {
-    case EPI_BF16: return launch256s<EPI_BF16, 4>(a, s), true;
-    case EPI_GELU_BF16: return launch256s<EPI_GELU_BF16, 4>(a, s), true;
-    case EPI_RESID_F32: return launch256s<EPI_RESID_F32, 4>(a, s), true;
-    case EPI_F32: return launch256s<EPI_F32, 4>(a, s), true;
-    case EPI_POS_F32: return launch256s<EPI_POS_F32, 4>(a, s), true;
-    default: return false;
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1901,94 +1880,42 @@ __global__ __launch_bounds__(512) void gemm128w_kernel(const GemmArgs args) {
   GEMM_STAMP(3);
 }
 
-static int super_rows(int tiles_m, int K);
-
 template <int EPI>
-static void launch128w(const GemmArgs& a0, hipStream_t s) {
-  GemmArgs a = a0;
-  const int tiles_m = (a.M + 127) / 128;
-  a.gm = super_rows(tiles_m, a.K);
-  hipLaunchKernelGGL((gemm128w_kernel<EPI>), dim3(tiles_m * (a.N / 256), 1, a.groups), dim3(512), 0, s, a);
-}
-
-static bool launch128w_epi(const GemmArgs& a, int epi, hipStream_t s) {
-  if (a.N % 256 || a.K % 32 || a.K < 32 || a.amode != A_DENSE) return false;
-  switch (epi) {
-    case EPI_RESID_F32: return launch128w<EPI_RESID_F32>(a, s), true;
-    case EPI_F32: return launch128w<EPI_F32>(a, s), true;
-    case EPI_POS_F32: return launch128w<EPI_POS_F32>(a, s), true;
-    default: return false;
-  }
-}
-
-// super-tile height (tile rows walked together, column-major inside): 8 rows x all columns keeps a short-K
-// GEMM's weight slab shared per XCD; a long-K GEMM (fc2: K = 3072; the head conv: K = 6912) re-fetches its
-// large A row blocks once per column tile unless the row's column tiles run close together (gm = 4: head
-// conv 359 -> 331 us at 32 sequences, fc2 level, tests/sweep_gm_b32.sh; +0.5 % over gm = 2, ab_env.sh)
-static int super_rows(int tiles_m, int K) {
-  static const int gm_env = getenv("MMT_GM") ? atoi(getenv("MMT_GM")) : 0;
-  static const int gm_long = getenv("MMT_GM_LONGK") ? atoi(getenv("MMT_GM_LONGK")) : 4;
-  const int gm = gm_env > 0 ? gm_env : (K >= 2048 ? gm_long : 8);
-  return tiles_m < gm ? tiles_m : gm;
+static void launch128w(const GemmArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((gemm128w_kernel<EPI>), dim3((a.M + 127) / 128 * (a.N / 256), 1, a.groups), dim3(512), 0, s, a);
 }
 
 template <int BM, int BN, int WMW, int WNW, int EPI, int AM, bool SPLIT, int ST, int BK = 64>
-static void launch_one(const GemmArgs& a0, hipStream_t s) {
-  GemmArgs a = a0;
-  const int tiles_m = (a.M + BM - 1) / BM, tiles_n = a.N / BN;
-  (void)tiles_n;
-  a.gm = super_rows(tiles_m, a.K);
-  dim3 grid(tiles_m * tiles_n, 1, a.groups);
+static void launch_one(const GemmArgs& a, hipStream_t s) {
+  dim3 grid((a.M + BM - 1) / BM * (a.N / BN), 1, a.groups);
   hipLaunchKernelGGL((gemm_kernel<BM, BN, WMW, WNW, EPI, AM, SPLIT, ST, BK>), grid, dim3(WMW * WNW * 64), 0, s, a);
 }
 
 template <int EPI>
-static void launch_persist(const GemmArgs& a0, hipStream_t s) {
-  GemmArgs a = a0;
-  const int tiles_m = (a.M + 127) / 128, ntiles = tiles_m * (a.N / 128);
-  a.gm = tiles_m < 8 ? tiles_m : 8;
+static void launch_persist(const GemmArgs& a, hipStream_t s) {
+  const int ntiles = (a.M + 127) / 128 * (a.N / 128);
   static const int slots = 2 * num_cus();   // two 64-KB-LDS workgroups per CU
   const int grid = (ntiles < slots ? ntiles : slots) & ~7;
   hipLaunchKernelGGL((gemm_persist_kernel<128, 128, 4, 2, EPI>), dim3(grid), dim3(512), 0, s, a);
 }
 
 template <int BM, int BN, int WMW, int WNW, int EPI, int NS, int BK, int WG_PER_CU>
-static void launch_ring(const GemmArgs& a0, hipStream_t s) {
-  GemmArgs a = a0;
-  const int tiles_m = (a.M + BM - 1) / BM, ntiles = tiles_m * (a.N / BN);
-  a.gm = tiles_m < 8 ? tiles_m : 8;
+static void launch_ring(const GemmArgs& a, hipStream_t s) {
+  const int ntiles = (a.M + BM - 1) / BM * (a.N / BN);
   static const int slots = WG_PER_CU * num_cus();
   int grid = (ntiles < slots ? ntiles : slots) & ~7;
   if (grid < 8) grid = 8;
   hipLaunchKernelGGL((gemm_ring_kernel<BM, BN, WMW, WNW, EPI, NS, BK>), dim3(grid), dim3(WMW * WNW * 64), 0, s, a);
 }
 
-template <int BM, int BN, int WMW, int WNW, int NS, int BK, int WG_PER_CU>
-static bool launch_ring_epi(const GemmArgs& a, int epi, hipStream_t s) {
-  // K / BK >= NS: a tile's bias (issued after the previous epilogue) has landed before its own epilogue
-  if (a.N % BN != 0 || a.groups != 1 || a.amode != A_DENSE || a.K % BK != 0 || a.K / BK < NS) return false;
-  if (epi == EPI_BF16) return launch_ring<BM, BN, WMW, WNW, EPI_BF16, NS, BK, WG_PER_CU>(a, s), true;
-  if (epi == EPI_GELU_BF16) return launch_ring<BM, BN, WMW, WNW, EPI_GELU_BF16, NS, BK, WG_PER_CU>(a, s), true;
-  return false;
-}
-
 template <int BM, int BN, int WMW, int WNW, bool SPLIT, int ST = 2, int BK = 64>
 static void launch_cfg(const GemmArgs& a, int epi, hipStream_t s) {
   if (a.amode == A_CONV3) {
-    if constexpr (BK == 64) {   // the conv gather walks 64-channel K-tiles
-      if (epi == EPI_RELU_BF16) return launch_one<BM, BN, WMW, WNW, EPI_RELU_BF16, A_CONV3, SPLIT, ST>(a, s);
-      if (epi == EPI_RELU_F32) return launch_one<BM, BN, WMW, WNW, EPI_RELU_F32, A_CONV3, SPLIT, ST>(a, s);
-    }
+    if constexpr (BK == 64)   // the conv gather walks 64-channel K-tiles
+      with_epi<kEpiRelu>(epi, [&](auto e) { launch_one<BM, BN, WMW, WNW, EPI_OF(e), A_CONV3, SPLIT, ST>(a, s); });
     return;
   }
-  switch (epi) {
-    case EPI_BF16: return launch_one<BM, BN, WMW, WNW, EPI_BF16, A_DENSE, SPLIT, ST, BK>(a, s);
-    case EPI_GELU_BF16: return launch_one<BM, BN, WMW, WNW, EPI_GELU_BF16, A_DENSE, SPLIT, ST, BK>(a, s);
-    case EPI_RESID_F32: return launch_one<BM, BN, WMW, WNW, EPI_RESID_F32, A_DENSE, SPLIT, ST, BK>(a, s);
-    case EPI_F32: return launch_one<BM, BN, WMW, WNW, EPI_F32, A_DENSE, SPLIT, ST, BK>(a, s);
-    case EPI_POS_F32: return launch_one<BM, BN, WMW, WNW, EPI_POS_F32, A_DENSE, SPLIT, ST, BK>(a, s);
-    default: break;
-  }
+  with_epi<kEpiDense>(epi, [&](auto e) { launch_one<BM, BN, WMW, WNW, EPI_OF(e), A_DENSE, SPLIT, ST, BK>(a, s); });
 }
 
 // split-K reduction: C = epi(sum_s partial_s + bias) in a fixed order (deterministic)
@@ -2005,252 +1932,73 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs args)
   store4<EPI, SPLIT>(g, args, m, n, acc);
 }
 
-// K splits of the last gemm() call on this host thread (1: no split); with defer_reduce a split run leaves its
-// slabs for the consumer (RowReduce, kernels.h) and skips the reduce launch
-static thread_local int g_last_ks = 1;
-constexpr int kMaxDeferKs = 8;   // tokens.hip apply_reduce holds at most this many slabs per row
-
+// split K: the slices' raw partial sums (EPI_PARTIAL), then -- unless the consumer combines the slabs (defer:
+// RowReduce, kernels.h) -- the reduce launch with the epilogue
 template <int BM, int BN, int WMW, int WNW, int AM, bool SPLIT, int ST>
-static void launch_splitk(const GemmArgs& a0, int epi, int ks, hipStream_t s) {
-  GemmArgs a = a0;
-  a.ksplit = ks;
-  const int tiles_m = (a.M + BM - 1) / BM;
-  a.gm = tiles_m < 8 ? tiles_m : 8;
-  if (a.defer_reduce && a.groups == 1 && epi == EPI_RESID_F32 && ks <= kMaxDeferKs) {
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, WMW, WNW, EPI_PARTIAL, AM, SPLIT, ST>), dim3(tiles_m * (a.N / BN), ks, 1),
-                       dim3(WMW * WNW * 64), 0, s, a);
-    g_last_ks = ks;
-    return;
-  }
-  hipLaunchKernelGGL((gemm_kernel<BM, BN, WMW, WNW, EPI_PARTIAL, AM, SPLIT, ST>), dim3(tiles_m * (a.N / BN), ks, a.groups),
+static void launch_splitk(const GemmArgs& a, int epi, bool defer, hipStream_t s) {
+  const int tiles = (a.M + BM - 1) / BM * (a.N / BN);
+  hipLaunchKernelGGL((gemm_kernel<BM, BN, WMW, WNW, EPI_PARTIAL, AM, SPLIT, ST>), dim3(tiles, a.ksplit, defer ? 1 : a.groups),
                      dim3(WMW * WNW * 64), 0, s, a);
+  if (defer) return;
   const dim3 rg((unsigned)(((int64_t)a.M * a.N / 4 + 255) / 256), 1, a.groups);
-  switch (epi) {
-    case EPI_BF16: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_BF16, SPLIT>), rg, dim3(256), 0, s, a); break;
-    case EPI_GELU_BF16: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_GELU_BF16, SPLIT>), rg, dim3(256), 0, s, a); break;
-    case EPI_RESID_F32: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_RESID_F32, SPLIT>), rg, dim3(256), 0, s, a); break;
-    case EPI_RELU_BF16: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_RELU_BF16, SPLIT>), rg, dim3(256), 0, s, a); break;
-    case EPI_F32: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_F32, SPLIT>), rg, dim3(256), 0, s, a); break;
-    case EPI_RELU_F32: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_RELU_F32, SPLIT>), rg, dim3(256), 0, s, a); break;
-    case EPI_POS_F32: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_POS_F32, SPLIT>), rg, dim3(256), 0, s, a); break;
-    default: break;
+  with_epi<kEpiAll>(epi, [&](auto e) { hipLaunchKernelGGL((splitk_reduce_kernel<EPI_OF(e), SPLIT>), rg, dim3(256), 0, s, a); });
+}
+
+// one gemm_kernel tile of MMT_GEMM_KERNEL_TILES in the precisions (and the split-K variant) it is built for
+template <int BM, int BN, int WMW, int WNW, int ST, int BK, int MODES, bool SPLIT>
+static void launch_tile(const GemmPlan& p, const GemmArgs& a, int epi, hipStream_t s) {
+  if constexpr ((MODES & (SPLIT ? 2 : 1)) != 0) {
+    if constexpr ((MODES & 4) != 0) {
+      if (p.ksplit > 1) {
+        if (a.amode == A_CONV3) return launch_splitk<BM, BN, WMW, WNW, A_CONV3, SPLIT, ST>(a, epi, p.defer, s);
+        return launch_splitk<BM, BN, WMW, WNW, A_DENSE, SPLIT, ST>(a, epi, p.defer, s);
+      }
+    }
+    launch_cfg<BM, BN, WMW, WNW, SPLIT, ST, BK>(a, epi, s);
+  }
+}
+
+// the one place a decision becomes a launch
+static void launch_plan(const GemmPlan& p, const GemmArgs& a0, int epi, hipStream_t s) {
+  GemmArgs a = a0;
+  a.gm = p.gm;
+  a.ksplit = p.ksplit;
+  switch (p.tile) {
+#define X(BM, BN, WMW, WNW, ST, BK, MODES)                                                   \
+  case GemmTile::MMT_TILE_ID(BM, BN, WMW, WNW, ST, BK):                                      \
+    return a.split ? launch_tile<BM, BN, WMW, WNW, ST, BK, MODES, true>(p, a, epi, s)        \
+                   : launch_tile<BM, BN, WMW, WNW, ST, BK, MODES, false>(p, a, epi, s);
+    MMT_GEMM_KERNEL_TILES(X)
+#undef X
+#define X(BM, BN, WMW, WNW, NS, BK, WG)                 \
+  case GemmTile::MMT_RING_ID(BM, BN, WMW, WNW, NS, BK): \
+    return with_epi<kEpi16>(epi, [&](auto e) { launch_ring<BM, BN, WMW, WNW, EPI_OF(e), NS, BK, WG>(a, s); });
+    MMT_GEMM_RING_TILES(X)
+#undef X
+    case GemmTile::PERSIST: return with_epi<kEpi16>(epi, [&](auto e) { launch_persist<EPI_OF(e)>(a, s); });
+    case GemmTile::G256: return with_epi<kEpiDense>(epi, [&](auto e) { launch256<EPI_OF(e)>(a, s); });
+    case GemmTile::G256S: return with_epi<kEpiDense>(epi, [&](auto e) { launch256s<EPI_OF(e), 4>(a, s); });
+    case GemmTile::G256S_320: return with_epi<kEpi16>(epi, [&](auto e) { launch256s<EPI_OF(e), 5>(a, s); });   // 320 x 256
+    case GemmTile::G128W: return with_epi<kEpiF32>(epi, [&](auto e) { launch128w<EPI_OF(e)>(a, s); });
+    case GemmTile::NONE: return;
   }
 }
 
 static int g_force_cfg = -1;   // tuning override (mmt_gemm_force_config), -1 = heuristic
 
-template <bool SPLIT>
-static void gemm_dispatch(const GemmArgs& a, int epi, hipStream_t s) {
-  if constexpr (SPLIT) {   // tuning override of the f16x3 tile (MMT_SPLIT_CFG), dense A only
-    static const int scfg = getenv("MMT_SPLIT_CFG") ? atoi(getenv("MMT_SPLIT_CFG")) : -1;
-    if (scfg >= 0 && a.amode == A_DENSE) {
-      switch (scfg) {
-        case 0: return launch_cfg<128, 128, 4, 2, true, 2, 64>(a, epi, s);
-        case 1: return launch_cfg<256, 128, 4, 2, true, 3, 32>(a, epi, s);
-        case 2: return launch_cfg<128, 128, 2, 2, true, 2, 64>(a, epi, s);
-        case 3: return launch_cfg<128, 128, 2, 2, true, 3, 32>(a, epi, s);
-        case 4: return launch_cfg<256, 128, 4, 2, true, 2, 32>(a, epi, s);
-        case 5: return launch_cfg<128, 256, 2, 4, true, 3, 32>(a, epi, s);
-        case 6: return launch_cfg<256, 256, 2, 4, true, 2, 32>(a, epi, s);
-        case 7: return launch_cfg<128, 128, 4, 2, true, 3, 32>(a, epi, s);
-        case 8: return launch_cfg<128, 64, 2, 2, true, 2, 64>(a, epi, s);
-        case 9: return launch_cfg<128, 128, 4, 2, true, 2, 32>(a, epi, s);
-        case 10: return launch_cfg<128, 128, 2, 2, true, 2, 32>(a, epi, s);
-        case 11: return launch_cfg<128, 64, 2, 2, true, 2, 32>(a, epi, s);
-        case 12: return launch_cfg<128, 128, 4, 2, true, 4, 32>(a, epi, s);
-        case 13: return launch_cfg<128, 256, 2, 4, true, 2, 32>(a, epi, s);
-        case 14: if (launch256s_epi(a, epi, s)) return; break;
-        case 15: if (a.N >= 2048 && launch256s_epi(a, epi, s)) return; break;
-        case 16: return launch_cfg<64, 64, 2, 2, true, 8, 32>(a, epi, s);
-        case 17: return launch_cfg<64, 64, 2, 2, true, 4, 32>(a, epi, s);
-        case 18: return launch_cfg<64, 64, 2, 2, true, 6, 32>(a, epi, s);
-        case 19: return launch_cfg<64, 64, 2, 2, true, 3, 64>(a, epi, s);
-        default: break;
-      }
-    }
-  }
-  if constexpr (SPLIT) {
-    // f16x3: the 8-phase 256 x 256 kernel where there are enough 256-wide column tiles (qkv, fc1: 250-300
-    // TF/s vs 240-250 for the 2-barrier 128 x 128 kernel); N = 768 stays on 128-row tiles (3 column tiles of
-    // 256 leave most CUs idle)
-    static const int t256_min = getenv("MMT_256S_MIN") ? atoi(getenv("MMT_256S_MIN")) : 128;
-    // the residual GEMMs (fc2, proj: N = 768) on the eight-phase kernel where its 256 x 256 tiles fill at least three
-    // quarters of a round of the chip, counting the concurrent stream part: OSTrack-384's 720- and 548-token layers
-    // (270 / 210 tiles; OSTrack 2 987 -> 3 045 frames/s with fc2 and proj at a full round, r06_ab_resid_256s.txt).  The
-    // ViT layers' 120 tiles stay on the 128-row kernels: fc2 there lost 10 % (four times the work per tile lengthens
-    // each stream half's chain).  MMT_RESID_256S: 0 never, 2 always (tuning)
-    static const int resid_256s = getenv("MMT_RESID_256S") ? atoi(getenv("MMT_RESID_256S")) : 1;
-    if (resid_256s && epi == EPI_RESID_F32 && a.groups == 1 && a.N % 256 == 0 &&
-        (resid_256s == 2 || 4 * (a.conc > 1 ? a.conc : 1) * ((a.M + 255) / 256) * (a.N / 256) >= 3 * num_cus()) &&
-        launch256s_epi(a, epi, s))
-      return;
-    // 320 x 256 tiles where they take fewer rounds of the one-workgroup-per-CU slots than 256 x 256 ones by more than
-    // their 1.25x work per tile, counting the concurrent stream part (qkv of the 244-token layers, fc1 of the
-    // 190-token ones at 2 x 16 sequences: two rounds -> one; OSTrack-384 2 914 -> 3 000 frames/s, r06_ab_t320_ostrack.txt;
-    // ties, 5 rounds of 320-row tiles for 5 of 256-row ones, measured -0.6 %).  MMT_T320: 0 never, 1 the rule, 2 always
-    // (tuning)
-    static const int t320 = getenv("MMT_T320") ? atoi(getenv("MMT_T320")) : 1;
-    bool use320 = false;
-    if (t320 && a.groups == 1 && (epi == EPI_BF16 || epi == EPI_GELU_BF16)) {
-      const int conc = a.conc > 1 ? a.conc : 1, slots = num_cus();
-      const int r256 = (conc * ((a.M + 255) / 256) * (a.N / 256) + slots - 1) / slots;
-      const int r320 = (conc * ((a.M + 319) / 320) * (a.N / 256) + slots - 1) / slots;
-      use320 = t320 == 2 || 5 * r320 < 4 * r256;
-    }
-    // 128 x 256 two-group tiles (gemm128w_kernel) for the fp32-output N = 768 GEMMs where the 256-row kernel's tiles
-    // would leave most CUs idle.  MMT_W256: 0 never, 1 the rule, 2 always (tuning); mmt_gemm_force_config(128) pins it
-    static const int w256 = getenv("MMT_W256") ? atoi(getenv("MMT_W256")) : 1;
-    if (g_force_cfg == 128 && launch128w_epi(a, epi, s)) return;
-    if (w256 && g_force_cfg < 0 && epi == EPI_RESID_F32 && a.groups == 1 && a.N % 256 == 0 && a.N < 2048) {
-      // the rule: its tiles fill at least 90 % of one round of the one-workgroup-per-CU slots, counting the concurrent
-      // stream part, where 128 x 128 tiles would take two rounds or more
-      const int conc = a.conc > 1 ? a.conc : 1, slots = num_cus();
-      const int tw = conc * ((a.M + 127) / 128) * (a.N / 256), t128 = conc * ((a.M + 127) / 128) * (a.N / 128);
-      if ((w256 == 2 || (tw <= slots && 10 * tw >= 9 * slots && t128 > slots)) && launch128w_epi(a, epi, s)) return;
-    }
-    const bool forced = g_force_cfg == 320 || g_force_cfg == 256;   // tests: pin the tile (any tile count)
-    if (forced) use320 = g_force_cfg == 320 && (epi == EPI_BF16 || epi == EPI_GELU_BF16);
-    if ((a.N >= 2048 || forced) && ((a.M + 255) / 256 * (a.N / 256) * a.groups >= t256_min || forced) &&
-        launch256s_epi(a, epi, s, use320))
-      return;
-  }
-  if constexpr (!SPLIT) {
-    if (g_force_cfg >= 0 && a.amode == A_DENSE) {
-      switch (g_force_cfg) {
-        case 1: return launch_cfg<256, 128, 4, 2, false, 3>(a, epi, s);
-        case 2: return launch_cfg<256, 128, 4, 2, false, 2>(a, epi, s);
-        case 3: return launch_cfg<128, 128, 2, 2, false, 2>(a, epi, s);
-        case 4: return launch_cfg<128, 128, 2, 2, false, 3>(a, epi, s);
-        case 5: return launch_cfg<128, 128, 4, 2, false, 2>(a, epi, s);
-        case 6: return launch_cfg<256, 256, 4, 2, false, 2>(a, epi, s);
-        case 7: return launch_cfg<128, 256, 2, 4, false, 2>(a, epi, s);
-        case 8: return launch_cfg<64, 128, 2, 2, false, 2>(a, epi, s);
-        case 9: if (a.N % 256 == 0) return launch256_epi(a, epi, s); break;
-        case 11: return launch_cfg<128, 128, 4, 2, false, 4, 32>(a, epi, s);
-        case 12: return launch_cfg<128, 128, 4, 2, false, 3, 32>(a, epi, s);
-        case 13: return launch_cfg<128, 64, 2, 2, false, 4, 32>(a, epi, s);
-        case 14: return launch_cfg<256, 128, 4, 2, false, 3, 32>(a, epi, s);
-        case 15: return launch_cfg<256, 128, 4, 2, false, 4, 32>(a, epi, s);
-        case 16: if (launch_ring_epi<256, 128, 4, 2, 3, 32, 2>(a, epi, s)) return; break;
-        case 17: if (launch_ring_epi<128, 128, 4, 2, 4, 32, 2>(a, epi, s)) return; break;
-        case 18: if (launch_ring_epi<128, 128, 4, 2, 2, 64, 2>(a, epi, s)) return; break;
-        case 19: if (launch_ring_epi<256, 256, 4, 2, 3, 32, 1>(a, epi, s)) return; break;
-        case 20: if (launch_ring_epi<256, 128, 4, 2, 2, 64, 1>(a, epi, s)) return; break;
-        case 21: return launch_cfg<128, 64, 4, 2, false, 2>(a, epi, s);
-        case 22: return launch_cfg<64, 128, 2, 4, false, 2>(a, epi, s);
-        case 23: return launch_cfg<128, 64, 4, 2, false, 3>(a, epi, s);
-        case 24: return launch_cfg<64, 128, 2, 4, false, 3>(a, epi, s);
-        case 10:
-          if (a.N % 128 == 0 && a.groups == 1 && (epi == EPI_BF16 || epi == EPI_GELU_BF16))
-            return epi == EPI_BF16 ? launch_persist<EPI_BF16>(a, s) : launch_persist<EPI_GELU_BF16>(a, s);
-          break;
-        default: break;
-      }
-    }
-  }
-  // Measured on the path's shapes (tests/bench_gemm.py, MI355X): 128x128 tiles with 8 waves (32x64
-  // per wave) and a 2-deep LDS ring (64 KB, two workgroups per CU, so one tile's prologue/epilogue
-  // overlaps the other's MFMAs) beat 256x128 / 256x256 / 3-deep rings on every K=768/3072 GEMM.
-  const int target = 200;   // aim for at least ~one tile per CU of the 256
-  const int t128 = (a.M + 127) / 128, t64 = (a.M + 63) / 64;
-  // bf16-output GEMMs with several 128 x 128 tiles per workgroup slot: the persistent kernel (the next
-  // tile's first K-tile loads under the current tile's tail)
-  static const int persist_min = getenv("MMT_PERSIST_MIN") ? atoi(getenv("MMT_PERSIST_MIN")) : 1;
-  if (!SPLIT && persist_min > 0 && a.amode == A_DENSE && a.groups == 1 && a.N % 128 == 0 &&
-      t128 * (a.N / 128) >= persist_min * 2 * num_cus()) {
-    if (epi == EPI_BF16) return launch_persist<EPI_BF16>(a, s);
-    if (epi == EPI_GELU_BF16) return launch_persist<EPI_GELU_BF16>(a, s);
-  }
-  // a little under one 128 x 128 tile per CU (the N = 768 GEMMs of the CE-pruned layers): 128 x 64 tiles
-  // with 8 waves put two workgroups on most CUs (fc2 at M = 4896: 41.4 -> 34.8 us)
-  const int t128n = t128 * (a.N / 128) * a.groups;
-  if constexpr (SPLIT) {
-    // f16x3 N = 768 GEMMs (proj, fc2, patch): 128 x 128 tiles from 128 tiles up -- every M of the path in a
-    // two-stream half (the 128 x 64 tiles that suit bf16's under-filled launches are slower here: the split
-    // GEMMs are 3x longer per tile, and the other half fills the tail; from 64 tiles: +1.8 % vs 200 and +1.9 %
-    // more vs 128 once the head convs (grouped, N = 3 x 128) take it too, sweep_t128.sh / ab_env.sh); a short
-    // K streams 32-deep K-tiles (proj 51 -> 48 us, patch 98 -> 85 us at 32 sequences, tests/sweep_split_cfg_b32.sh),
-    // fc2's K = 3072 keeps 64-deep ones (144 -> 135 us)
-    static const int t128_min = getenv("MMT_SPLIT_T128") ? atoi(getenv("MMT_SPLIT_T128")) : 64;
-    // (not for one sequence's few rows: fc1 at M = 320 keeps 240 64 x 64 workgroups instead of 72; the head's implicit
-    // 3x3 conv, A_CONV3 with K = 6912, gathers 64-channel K-tiles)
-    if (a.N % 128 == 0 && t128n >= t128_min && t128 >= 8) {
-      // 128 x 192 tiles where all of them fit one round of the chip's one-workgroup-per-CU slots and 128 x 128 tiles
-      // would take two or more, counting the launches of the other stream parts that run beside this one (a.conc):
-      // the head's conv1 at 2 x 16 sequences (256 tiles in one round instead of 384: 287 -> 196 us alone), fc2 / proj
-      // after candidate elimination (fc2 123.6 -> 107.4 us per launch; the line +0.8 %, profiles/r05_ab_t192.txt).
-      // Where the 192-wide tiles take several rounds too (OSTrack-384's long layers: 3 against 5) they lost 1 %, so
-      // a one-round fit is the rule.  MMT_T192: 0 never, 2 always (tuning)
-      static const int t192 = getenv("MMT_T192") ? atoi(getenv("MMT_T192")) : 1;
-      if (t192 && a.N % 192 == 0 && a.groups == 1 && (a.amode == A_CONV3 || a.K % 64 == 0)) {
-        const int conc = a.conc > 1 ? a.conc : 1, slots = num_cus();
-        const int r128 = (conc * t128 * (a.N / 128) + slots - 1) / slots;
-        const int r192 = (conc * t128 * (a.N / 192) + slots - 1) / slots;
-        if (t192 == 2 || (r192 == 1 && r128 >= 2)) return launch_cfg<128, 192, 4, 2, true, 2, 64>(a, epi, s);
-      }
-      // (the N = 768 GEMMs -- proj, patch -- take the register-pipelined 64-deep tile since it exists: proj at one
-      // half's rows 31 -> 25 us (5 120 rows) .. 27 -> 22 us (2 432), tests/r3_run33.sh; the wide qkv / fc1 fallbacks
-      // keep the 32-deep ring, level or better there)
-      if (a.K <= 1024 && a.amode == A_DENSE && a.N > 768) return launch_cfg<128, 128, 4, 2, true, 2, 32>(a, epi, s);
-      return launch_cfg<128, 128, 4, 2, true, 2, 64>(a, epi, s);
-    }
-  }
-  if (a.N % 128 == 0 && t128n >= target && t128n < num_cus()) return launch_cfg<128, 64, 4, 2, SPLIT>(a, epi, s);
-  if (a.N % 128 == 0 && t128n >= target) return launch_cfg<128, 128, 4, 2, SPLIT>(a, epi, s);
-  if (a.N % 64 == 0) {
-    if (t128 * (a.N / 64) * a.groups >= target) return launch_cfg<128, 64, 2, 2, SPLIT>(a, epi, s);
-    // few 64 x 64 tiles and a long K (small batches): split K over workgroups (fp32 partials in the
-    // workspace, fixed-order reduction with the epilogue), at least 4 K-tiles per split
-    const int tiles = t64 * (a.N / 64) * a.groups, nk = a.K / 64;
-    // (100, not 128: qkv of the 129..192-row CE layers at one sequence -- 108 tiles -- runs unsplit without its
-    // reduce launch, 1092 -> 1100 frames/s, profiles/r05_ab_splitk_tiles_b1.txt)
-    static const int sk_tiles = getenv("MMT_SPLITK_TILES") ? atoi(getenv("MMT_SPLITK_TILES")) : 100;
-    static const int sk_target = getenv("MMT_SPLITK_TARGET") ? atoi(getenv("MMT_SPLITK_TARGET")) : 256;
-    static const int sk_minkt = getenv("MMT_SPLITK_MINKT") ? atoi(getenv("MMT_SPLITK_MINKT")) : 4;
-    static const int sk_max = getenv("MMT_SPLITK_MAX") ? atoi(getenv("MMT_SPLITK_MAX")) : 8;
-    // slices per tile rounded DOWN, so the slices of every tile run in one round of workgroups (fc2 at one
-    // sequence: 60 tiles x 4 = 240 workgroups of 768-deep slices beat 300 of 614 that take two rounds on 44
-    // CUs; 823 -> 906 frames/s, round 2).  64 x 64 few-tile GEMMs with 8 waves (16 x 32 each): twice
-    // the waves issuing each K-tile's LDS-DMA loads -- at one sequence these GEMMs are bound by what a CU can take in
-    // (one tile per CU, ~400 KB of hi + lo operands at ~45 GB/s), 906 -> 929 frames/s against 4 waves
-    // (tests/few_w8_ab.sh)
-    if (a.ws && a.ws_elems > 0 && tiles < sk_tiles && nk >= 2 * sk_minkt) {
-      int ks = sk_target / tiles;
-      ks = ks < nk / sk_minkt ? ks : nk / sk_minkt;
-      ks = ks < sk_max ? ks : sk_max;
-      while (ks > 1 && (int64_t)ks * a.groups * a.M * a.N > a.ws_elems) --ks;
-      if (ks > 1) {
-        // f16x3: a 3-deep ring (96 KB of LDS) beat 4-deep at one sequence (tests/sweep_ring_b1.sh)
-        constexpr int SKST = SPLIT ? 3 : 4;
-        if (a.amode == A_CONV3) return launch_splitk<64, 64, 4, 2, A_CONV3, SPLIT, SKST>(a, epi, ks, s);
-        return launch_splitk<64, 64, 4, 2, A_DENSE, SPLIT, SKST>(a, epi, ks, s);
-      }
-    }
-    // few tiles (small batches): each workgroup walks the whole K serially, so keep K-tiles in flight
-    // (bf16: 4-deep LDS ring, an 8-deep one measured no better at M = 320; f16x3: 3-deep, qkv 17.3 ->
-    // 15.4 us and fc1 16.8 -> 16.5 us at one sequence, tests/sweep_ring_b1.sh)
-    if (a.K >= 6 * 64) return launch_cfg<64, 64, 4, 2, SPLIT, SPLIT ? 3 : 4>(a, epi, s);
-    return launch_cfg<64, 64, 2, 2, SPLIT>(a, epi, s);
-  }
-  if (t64 * (a.N / 32) * a.groups >= target) return launch_cfg<64, 32, 4, 1, SPLIT>(a, epi, s);
-  return launch_cfg<32, 32, 2, 1, SPLIT>(a, epi, s);
-}
-
-int gemm(const GemmArgs& a, int epi, hipStream_t s) {
-  g_last_ks = 1;
+int gemm(const GemmArgs& a, int epi, hipStream_t s, const char** error) {
+  static const GemmKnobs knobs = gemm_knobs_from_env();
+  const GemmShape sh{a.M, a.N, a.K, a.groups, a.amode, epi, a.split, a.conc, a.ws != nullptr, a.ws_elems, a.defer_reduce};
+  GemmPlan p = gemm_plan(sh, knobs, num_cus(), g_force_cfg);
   // the f16x3 16-bit epilogues (gemm_kernel's staged split epilogue, gemm256s) always store a lo plane: a caller
   // without one is a programming error, not a bf16 fallback
   if (a.split && epi_is_bf16(epi))
     for (int i = 0; i < a.groups; ++i)
-      if (!a.g[i].C_lo) {
-        fprintf(stderr, "mmt: f16x3 GEMM with a 16-bit epilogue needs C_lo (group %d)\n", i);
-        abort();
-      }
-  if (a.split)
-    gemm_dispatch<true>(a, epi, s);
-  else
-    gemm_dispatch<false>(a, epi, s);
-  return g_last_ks;
+      if (!a.g[i].C_lo) p.error = "f16x3 GEMM with a 16-bit epilogue needs C_lo";
+  if (error) *error = p.error;
+  if (p.error) return -1;
+  launch_plan(p, a, epi, s);
+  return p.defer ? p.ksplit : 1;
 }
 
 void gemm_force_config(int cfg) { g_force_cfg = cfg; }

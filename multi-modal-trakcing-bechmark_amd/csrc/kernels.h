@@ -4,22 +4,13 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace mmt {
 
 // ---------------------------------------------------------------- GEMM (MFMA bf16 -> fp32)
 // C[m][n] = epi( sum_k A[m][k] * W[n][k] + bias[n] ), A: M x K (lda), W: N x K (ldw), both bf16, K-contiguous.
-enum Epi : int {
-  EPI_BF16 = 0,        // bias -> bf16
-  EPI_GELU_BF16 = 1,   // bias, exact GELU -> bf16
-  EPI_RESID_F32 = 2,   // C(f32) = R(f32) + (acc + bias)
-  EPI_RELU_BF16 = 3,   // bias, ReLU -> bf16            (head conv, BN folded)
-  EPI_F32 = 4,         // bias -> f32
-  EPI_RELU_F32 = 5,    // bias, ReLU -> f32
-  EPI_POS_F32 = 6,     // C(f32) = (acc + bias) + R[m % pos_rows]  (OSTrack patch-embed + pos_embed)
-  EPI_PARTIAL = 7,     // internal (split-K): raw fp32 partial sums into the workspace
-};
-enum AMode : int { A_DENSE = 0, A_CONV3 = 1 };
+// (enum Epi, enum AMode: gemm_plan.h)
 
 struct GemmGroup {
   const bf16_t* A; const bf16_t* A_lo; int64_t lda;     // A_lo: low half of the split operand (SPLIT)
@@ -63,7 +54,8 @@ struct RowReduce {
 
 // returns the K splits it ran: 1, or (a.defer_reduce and few tiles) ks > 1 with the raw fp32 partial slabs left
 // in a.ws ([ks][M][N], one group) for the consumer to combine (RowReduce below) instead of a reduce launch
-int gemm(const GemmArgs& a, int epi, hipStream_t s);
+// -1, nothing launched and *error set: no kernel runs this shape / epilogue / A mode (gemm_plan), or C_lo is missing
+int gemm(const GemmArgs& a, int epi, hipStream_t s, const char** error = nullptr);
 void gemm_force_config(int cfg);   // tuning override, -1 = heuristic
 int gemm_set_stamps(void* dev_buf);  // tuning: per-block cycle stamps [blocks][4] (null: off)
 

@@ -2,9 +2,12 @@
 
 bench.py's headline line runs 32 sequences per mmt_track_batch launch with the launch sequence captured in a
 hipGraph and split into two stream halves of 16 sequences (engine.cpp enqueue_split), which selects a
-different kernel set from the one-sequence launches of test_gpu_parity.py: gemm256s_kernel<0/1> for qkv /
-fc1, the 128 x 128 f16x3 gemm_kernel for proj / fc2 / patch / head convs, attn_kernel<8, true> and no
-split-K.  Here every golden pair of tests/golden/net_*.npz (the reference network's own outputs,
+different kernel set from the one-sequence launches of test_gpu_parity.py (the tables of test_gemm_plan.py, by
+layer width): qkv / fc1 on gemm256s_kernel, its 320 x 256 variant at 244 / 190 tokens and the 128 x 128 f16x3
+gemm_kernel (32-deep K-tiles) in the narrowest layers; proj / fc2 on gemm128w_kernel at 320 tokens, 128 x 192
+gemm_kernel tiles at 244 / 190 tokens and 128 x 128 ones at 153; patch on 128 x 128 tiles; the head's conv1 on
+128 x 192 tiles, conv2-4 on 128 x 128 / 64 x 64 / 32 x 32 ones; attn_kernel<8, true> and no split-K
+(OSTrack-384's wider layers: test_gemm_plan.py OSTRACK384_B32).  Here every golden pair of tests/golden/net_*.npz (the reference network's own outputs,
 make_golden.py) sits in one slot of such a 32-sequence launch -- the halves' edge slots 0, 15, 16, 31 first --
 with random pairs in the other slots; the launch is run once eagerly (the first use of a batch shape, which
 also captures it) and then replayed from the captured graph, and each golden slot is read back with
