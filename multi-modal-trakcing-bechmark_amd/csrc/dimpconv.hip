@@ -22,27 +22,17 @@
 // ends with 4 consecutive output channels of one pixel (16-B NHWC stores).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
-#include <algorithm>
 #include <type_traits>
-#include <vector>
-#include <cstdio>
 
 #include "../../include/mmtrack.h"
 #include "common.h"
+#include "conv_plan.h"
 
 namespace mmt {
 
 constexpr int kMaxShards = 64, kShardStride = 32;   // sharded max words: 64 x 128-B lines per tensor
 
-#if defined(CONV_STAMPS)   // tuning builds only: per-workgroup phase cycles of conv_f16x3_deep_kernel
-__device__ unsigned long long* g_conv_stamps = nullptr;   // [block][8]
-#define CSTAMP_T() (threadIdx.x == 0 ? __builtin_amdgcn_s_memtime() : 0ull)
-#else
-#define CSTAMP_T() 0ull
-#endif
-constexpr int kMaxGroups = 2, kMaxSplitK = 8;
 
 struct ConvGroupArgs {            // one convolution of a grouped launch (the RGB / aux backbones' twin layers)
   const float* x;                 // [N][H][W][Cin] fp32
@@ -65,11 +55,13 @@ struct ConvF16Args {
   ConvGroupArgs g[kMaxGroups];
   float* part;                    // split-K partials [ks][G][M][Cout] (ks > 1)
   int N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, Kp, ks;
+  // xcd_order and staged_epi (below): the host sets both to 1.  The fields and the kernel branches that read them
+  // stay so that every kernel's argument layout, and with it its code, is what was measured
   int xcd_order;                  // conv_f16x3_deep_kernel: XCD-aware tile order (else M tiles fastest)
   // a downsample fused into a 1 x 1 conv3 (conv_f16x3_deep_kernel only): K-tiles from Cin / 32 on read x2 at
   // output pixel (oy, ox) * stride2; 0: none
   int Cin2, H2, W2, stride2;
-  int staged_epi;                 // conv_f16x3_deep_kernel (BM 128): the LDS-staged epilogue
+  int staged_epi;                 // conv_f16x3_deep_kernel: the LDS-staged epilogue
 };
 
 __device__ __forceinline__ int cswz(int r, int c) { return r * 32 + ((c ^ ((r >> 2) & 2)) << 3); }   // gemm.hip swzk<32>
@@ -213,7 +205,9 @@ __device__ __forceinline__ float conv_store_tile_staged(const ConvGroupArgs& g, 
       if (g.bias)
         v = f32x4{__builtin_fmaf(acc[i][j][0], inv, bv[0]), __builtin_fmaf(acc[i][j][1], inv, bv[1]),
                   __builtin_fmaf(acc[i][j][2], inv, bv[2]), __builtin_fmaf(acc[i][j][3], inv, bv[3])};
-      *reinterpret_cast<f32x4*>(lds + r * BN + (((c >> 2) ^ (r & 7)) << 2)) = v;
+      // (| for +: the row base is a multiple of BN, the chunk offset below BN; spelled as one index, so the address
+      // code does not depend on what the compiler knows of `lds` at its single call site)
+      *reinterpret_cast<f32x4*>(lds + (r * BN | (((c >> 2) ^ (r & 7)) << 2))) = v;
     }
   }
   __syncthreads();
@@ -396,23 +390,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
     l = lx | (uint32_t)ly << 16;
   };
   auto stash = [&](const ConvRegs& r, int st) {
-#if defined(CONV_EXP_NOSTASH)   // tuning experiment only: no A split / LDS write (wrong results)
-    if (r.a0.x == 12345.f) *reinterpret_cast<float*>(&sA[st][0][0]) = r.a0.y + r.a1.z;
-    return;
-#endif
     uint4 hv, lv;
-#if defined(CONV_EXP_HIONLY)    // tuning experiment only: hi halves, lo = 0 (wrong results)
-    hv.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(r.a0.x * sa, r.a0.y * sa));
-    hv.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(r.a0.z * sa, r.a0.w * sa));
-    hv.z = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(r.a1.x * sa, r.a1.y * sa));
-    hv.w = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(r.a1.z * sa, r.a1.w * sa));
-    lv = make_uint4(0, 0, 0, 0);
-#else
     pack2(r.a0.x, r.a0.y, hv.x, lv.x);
     pack2(r.a0.z, r.a0.w, hv.y, lv.y);
     pack2(r.a1.x, r.a1.y, hv.z, lv.z);
     pack2(r.a1.z, r.a1.w, hv.w, lv.w);
-#endif
     *reinterpret_cast<uint4*>(&sA[st][0][cswz(ar, ac)]) = hv;
     *reinterpret_cast<uint4*>(&sA[st][1][cswz(ar, ac)]) = lv;
   };
@@ -443,10 +425,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
 #pragma unroll
       for (int i = 0; i < FM; ++i) {
         acc[i][j] = mfma16<true>(bh, ah[i], acc[i][j]);
-#if !defined(CONV_EXP_ONEMFMA)  // tuning experiment only: one MFMA per product (wrong results)
         acc[i][j] = mfma16<true>(bl, ah[i], acc[i][j]);
         acc[i][j] = mfma16<true>(bh, al[i], acc[i][j]);
-#endif
       }
     }
   };
@@ -525,18 +505,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
 }
 
 // The stem (kh x kw / stride on a 4-channel image -- 3 channels padded with a zero one, mmt_image_normalize4 --
-// and 64 output channels) as 2-D tiles of 8 x 16 output pixels: the tile's input patch ((8 - 1) s + kh rows x
+// and 64 output channels) as 2-D tiles of 16 x 16 output pixels: the tile's input patch ((16 - 1) s + kh rows x
 // (16 - 1) s + kw columns, zeros outside the image) is loaded ONCE, split into fp16 hi / lo into LDS, and every
 // K-tile's A fragments are read from it (a tap is 4 channels, 8 B per half); the weights of all K-tiles arrive
 // by LDS-DMA alongside.  One dependent round trip per workgroup instead of one per K-tile
 // (conv_f16x3_kernel<64, true>: 7 K-tiles of register-staged gathers), with the same products in the same
 // order, so the output is that kernel's bit for bit.
-// TH: tile rows (8 or 16; 16 halves the weight re-fetch per output pixel, 79 KB of LDS: still two workgroups per CU)
-constexpr int kStemTW = 16, kStemMaxKt = 7;
-template <int TH>
+// 16 tile rows (against 8) halve the weight re-fetch per output pixel; 79 KB of LDS: still two workgroups per CU
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void conv_stem_f16x3_kernel(const ConvF16Args a) {
-  constexpr int kStemTH = TH, kStemMaxP = ((TH - 1) * 2 + 7) * ((kStemTW - 1) * 2 + 7), NPL = (kStemMaxP + 511) / 512;
-  constexpr int BN = 64, BK = 32, WN = BN / 2, FM = TH / 4, FN = WN / 16;
+  constexpr int kStemMaxP = ((kStemTH - 1) * 2 + 7) * ((kStemTW - 1) * 2 + 7), NPL = (kStemMaxP + 511) / 512;
+  constexpr int BN = 64, BK = 32, WN = BN / 2, FM = kStemTH / 4, FN = WN / 16;
   __shared__ __attribute__((aligned(16))) uint16_t sP[2][(kStemMaxP + 1) * 4];   // [hi, lo][pixel][4 ch]; + a zero pixel
   __shared__ __attribute__((aligned(16))) uint16_t sW[kStemMaxKt][2][BN * BK];
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -669,7 +647,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
 // bit for bit.  7 x 7 / stride 2 / 4 channels / 64 outputs only: K = 49 taps x 4 = 196, so the last of the seven
 // 32-deep K-tiles holds one tap and only its first 16-B chunk of each weight row is staged (the other three lanes'
 // fragments read the same finite weights against the zero pixel).
-constexpr int kPoolT = 8, kPoolS = 2 * kPoolT + 1, kPoolPx = kPoolS * kPoolS;   // 8 x 8 pooled, 17 x 17 stem
+constexpr int kPoolS = 2 * kPoolT + 1, kPoolPx = kPoolS * kPoolS;                // 8 x 8 pooled, 17 x 17 stem
 constexpr int kPoolPW = (kPoolS - 1) * 2 + 7, kPoolMaxP = kPoolPW * kPoolPW;      // 39 x 39 input pixels
 constexpr int kPoolHalf = (kPoolPW + 1) / 2;                                         // a row's even columns
 constexpr int kPoolLdsP = 2 * (kPoolMaxP + 1) * 4 * 2;                               // patch hi / lo (+ zero pixel)
@@ -870,32 +848,26 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void c
 // of the three MFMAs and the whole activation split / stash together saves only a third of the kernel's time.  Here
 // the activation loads are inline-asm buffer loads (the compiler neither counts nor waits for them; every wait is
 // written out, naming the registers it guards), so the weights can go two K-tiles ahead into the three-stage ring and
-// the activations NR K-tiles ahead into NR register sets without the compiler draining one queue to reach the other.
-// Step j issues W(j + 2) then A(j + NR), multiplies K-tile j, waits for A(j + 1) -- 2 (NW + NA) younger operations
-// (for NR = 3) -- and stashes it, then waits for W(j + 1) and passes the barrier.  Same products, same summation
-// order as conv_f16x3_kernel (bit-identical).
-// BM = 256 (tuning, MMT_CONV_BM=256): 64 x 64 per wave -- 16 fragment reads per 48 MFMAs instead of 12 per 24, one
-// barrier per 48 -- at one workgroup per CU (112 KB of LDS)
-// OVL: K-tile j + 1's activations are waited for BEFORE K-tile j is multiplied, and split and stashed in the same
-// scheduling region as its MFMAs (no inline asm between them), so the split's VALU work and the LDS stores issue
-// between the MFMAs instead of after them while every wave of the CU sits in the same phase between two barriers.
-template <int BN, int NR, int BM = 128, bool OVL = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ? 4 : 2))) void conv_f16x3_deep_kernel(
-    const ConvF16Args a) {
-  constexpr int BK = 32, NWS = 3;
+// the activations NR = 3 K-tiles ahead into three register sets without the compiler draining one queue to reach the
+// other.  Step j waits for A(j + 1) -- NW + NA younger operations -- BEFORE K-tile j is multiplied, issues W(j + 2)
+// then A(j + 3), and splits and stashes A(j + 1) in the same scheduling region as K-tile j's MFMAs (no inline asm
+// between them), so the split's VALU work and the LDS stores issue between the MFMAs instead of after them while every
+// wave of the CU sits in the same phase between two barriers; then it waits for W(j + 1) and passes the barrier.
+// Same products, same summation order as conv_f16x3_kernel (bit-identical).
+template <int BN>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void conv_f16x3_deep_kernel(const ConvF16Args a) {
+  constexpr int BM = 128, BK = 32, NWS = 3, NR = 3;
   constexpr int WN = BN / 2, FM = BM / 64, FN = WN / 16;
-  constexpr int SL = BM / 128;                 // activation slots (a row's 8 K values) per thread
   constexpr int NW = BN / 64;                  // W LDS-DMA pieces per wave per K-tile
-  constexpr int NA = 2 * SL;                   // A loads per thread per K-tile
-  constexpr int WAIT_A = (NR - 1) * (NW + NA); // younger operations when A(j + 1) is waited for
-  constexpr int WAIT_W = 2 * NA + NW;          // ... when W(j + 1) is (A(j + NR - 1), W(j + 2), A(j + NR))
-  constexpr int WAIT_AE = (NR - 2) * (NW + NA); // OVL: ... when A(j + 1) is, before step j's loads
-  static_assert(NR == 2 || NR == 3, "register sets");
+  constexpr int NA = 2;                        // A loads per thread per K-tile
+  constexpr int WAIT_A = (NR - 1) * (NW + NA); // younger operations when the prologue waits for A(0)
+  constexpr int WAIT_W = 2 * NA + NW;          // ... when W(j + 1) is waited for (A(j + 2), W(j + 2), A(j + 3))
+  constexpr int WAIT_AE = (NR - 2) * (NW + NA); // ... when A(j + 1) is, before step j's loads
   // one LDS array (the operand rings, then the epilogue's staged tile: 128 x BN floats <= its size)
   __shared__ __attribute__((aligned(16))) uint16_t smem_dk[2 * 2 * BM * BK + NWS * 2 * BN * BK];
   auto& sA = *reinterpret_cast<uint16_t(*)[2][2][BM * BK]>(smem_dk);
   auto& sW = *reinterpret_cast<uint16_t(*)[NWS][2][BN * BK]>(smem_dk + 2 * 2 * BM * BK);
-  static_assert(BM != 128 || 128 * BN * 4 <= (int)sizeof(smem_dk), "staged epilogue tile");
+  static_assert(128 * BN * 4 <= (int)sizeof(smem_dk), "staged epilogue tile");
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int grp = blockIdx.z / a.ks, slice = blockIdx.z - grp * a.ks;
@@ -905,8 +877,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
   // tile ids, N fastest, so the column-tile siblings of an activation tile run on one XCD and share its L2 (the
   // activation tile is fetched from beyond the L2 once per XCD instead of once per column tile)
   // (the default: mfDiMP 6 350 -> 6 394 frames/s in two rounds; applied only to wide outputs and short launches it
-  // measured level, although layer1 conv3 alone, without its residual, runs 128 -> 150 us in this order;
-  // MMT_CONV_XCD=0: M tiles fastest over the whole chip, profiles/r04_ab_conv_xcd_order.txt)
+  // measured level, although layer1 conv3 alone, without its residual, runs 128 -> 150 us in this order; against
+  // M tiles fastest over the whole chip, profiles/r04_ab_conv_xcd_order.txt)
   int m0, n0;
   {
     const int gn = a.Cout / BN, ntl = gridDim.x, b = blockIdx.x;
@@ -939,13 +911,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
   }
   const float inv = g.inv_w / sa;
 
-  const int ac = t & 3;   // slot s: row (t >> 2) + 128 s, K chunk ac (8 values)
-  bool mval[SL];
-  int iy0[SL], ix0[SL];
-  uint32_t xrow[SL], xrow2[SL];
+  const int ac = t & 3;   // A load slot: row (pixel) t >> 2, K chunk ac (8 values)
+  // (the slot's geometry stays the one-trip loop over one-element arrays it was measured as: the compiler promotes
+  // them only once the loop is unrolled, and written as scalars it allocates the whole kernel's registers differently)
+  bool mval[1];
+  int iy0[1], ix0[1];
+  uint32_t xrow[1], xrow2[1];
 #pragma unroll
-  for (int sl = 0; sl < SL; ++sl) {
-    const int m = m0 + (t >> 2) + 128 * sl;
+  for (int sl = 0; sl < 1; ++sl) {
+    const int m = m0 + (t >> 2);
     mval[sl] = m < M;
     iy0[sl] = ix0[sl] = 0;
     xrow[sl] = xrow2[sl] = 0;
@@ -968,7 +942,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
   const int cpt = a.Cin / BK;
 
   struct DeepRegs {   // native vectors: an inline-asm register operand, not a struct in memory
-    f32x4 a[2 * SL];
+    f32x4 a[2];
   };
   DeepRegs r[NR];
   // K-tile i of the slice (zeros past it: an out-of-range offset, no traffic) into register set `set`.  The calls
@@ -995,18 +969,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
     const bool second = kt0 + i >= nk1;
     const int c2 = (kt0 + i - nk1) * BK + ac * 8;
     const u32x4 qA = second ? qX2 : qX;
-#pragma unroll
-    for (int sl = 0; sl < SL; ++sl) {
-      const int iy = iy0[sl] + ky, ix = ix0[sl] + kx;
-      // (bitwise, not short-circuit: no control flow around the loads)
-      const bool inb = (iy >= 0) & (iy < a.H) & (ix >= 0) & (ix < a.W);
-      const bool ok = (i < nt) & mval[sl] & (second | inb);
-      const uint32_t off1 = xrow[sl] + (uint32_t)((iy * a.W + ix) * a.Cin + c0), off2 = xrow2[sl] + (uint32_t)c2;
-      const uint32_t vo = ok ? (second ? off2 : off1) * 4 : kBufOob;
-      asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(set.a[2 * sl]) : "v"(vo), "s"(qA) : "memory");
-      asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:16" : "=v"(set.a[2 * sl + 1]) : "v"(vo), "s"(qA)
-                   : "memory");
-    }
+    const int iy = iy0[0] + ky, ix = ix0[0] + kx;
+    // (bitwise, not short-circuit: no control flow around the loads)
+    const bool inb = (iy >= 0) & (iy < a.H) & (ix >= 0) & (ix < a.W);
+    const bool ok = (i < nt) & mval[0] & (second | inb);
+    const uint32_t off1 = xrow[0] + (uint32_t)((iy * a.W + ix) * a.Cin + c0), off2 = xrow2[0] + (uint32_t)c2;
+    const uint32_t vo = ok ? (second ? off2 : off1) * 4 : kBufOob;
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(set.a[0]) : "v"(vo), "s"(qA) : "memory");
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:16" : "=v"(set.a[1]) : "v"(vo), "s"(qA) : "memory");
   };
   const u32x4 qWh = make_rsrc_words(g.wh, (int64_t)a.Cout * a.Kp * 2);
   const u32x4 qWl = make_rsrc_words(g.wl, (int64_t)a.Cout * a.Kp * 2);
@@ -1028,17 +998,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
   // the register set's loads done: all but the CNT youngest vector-memory operations (the set named as read-write,
   // so nothing reads it above this point)
   auto wait_set = [&](DeepRegs& set, auto cnt) {
-    if constexpr (SL == 1)
-      asm volatile("s_waitcnt vmcnt(%2)" : "+v"(set.a[0]), "+v"(set.a[1]) : "n"(decltype(cnt)::value) : "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(%4)" : "+v"(set.a[0]), "+v"(set.a[1]), "+v"(set.a[2]), "+v"(set.a[3])
-                   : "n"(decltype(cnt)::value) : "memory");
+    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(set.a[0]), "+v"(set.a[1]) : "n"(decltype(cnt)::value) : "memory");
   };
   auto keep_set = [&](DeepRegs& set) {   // the set's registers live up to here (no code, no wait)
-    if constexpr (SL == 1)
-      asm volatile("" : "+v"(set.a[0]), "+v"(set.a[1]));
-    else
-      asm volatile("" : "+v"(set.a[0]), "+v"(set.a[1]), "+v"(set.a[2]), "+v"(set.a[3]));
+    asm volatile("" : "+v"(set.a[0]), "+v"(set.a[1]));
   };
   auto pack2 = [&](float x, float y, uint32_t& h, uint32_t& l) {
     uint16_t hx, lx, hy, ly;
@@ -1047,50 +1010,25 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
     h = hx | (uint32_t)hy << 16;
     l = lx | (uint32_t)ly << 16;
   };
-  auto stash = [&](const DeepRegs& rr, int st) {
-#pragma unroll
-    for (int sl = 0; sl < SL; ++sl) {
-      const f32x4 &x0 = rr.a[2 * sl], &x1 = rr.a[2 * sl + 1];
-      uint4 hv, lv;
-      pack2(x0[0], x0[1], hv.x, lv.x);
-      pack2(x0[2], x0[3], hv.y, lv.y);
-      pack2(x1[0], x1[1], hv.z, lv.z);
-      pack2(x1[2], x1[3], hv.w, lv.w);
-      const int ar = (t >> 2) + 128 * sl;
-      *reinterpret_cast<uint4*>(&sA[st][0][cswz(ar, ac)]) = hv;
-      *reinterpret_cast<uint4*>(&sA[st][1][cswz(ar, ac)]) = lv;
-    }
+  auto stash = [&](const DeepRegs& rr, int st) {   // the prologue's: K-tile 0, nothing to weave it into
+    const f32x4 &x0 = rr.a[0], &x1 = rr.a[1];
+    uint4 hv, lv;
+    pack2(x0[0], x0[1], hv.x, lv.x);
+    pack2(x0[2], x0[3], hv.y, lv.y);
+    pack2(x1[0], x1[1], hv.z, lv.z);
+    pack2(x1[2], x1[3], hv.w, lv.w);
+    const int ar = t >> 2;
+    *reinterpret_cast<uint4*>(&sA[st][0][cswz(ar, ac)]) = hv;
+    *reinterpret_cast<uint4*>(&sA[st][1][cswz(ar, ac)]) = lv;
   };
   f32x4 acc[FM][FN];
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto compute = [&](int sta, int stw) {
-    const int c = lane >> 4;
-    bf16x8 ah[FM], al[FM];
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-      const int row = wm * (BM / 4) + i * 16 + (lane & 15);
-      ah[i] = *reinterpret_cast<const bf16x8*>(&sA[sta][0][cswz(row, c)]);
-      al[i] = *reinterpret_cast<const bf16x8*>(&sA[sta][1][cswz(row, c)]);
-    }
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      const int row = wn * WN + j * 16 + (lane & 15);
-      const bf16x8 bh = *reinterpret_cast<const bf16x8*>(&sW[stw][0][cswz(row, c)]);
-      const bf16x8 bl = *reinterpret_cast<const bf16x8*>(&sW[stw][1][cswz(row, c)]);
-#pragma unroll
-      for (int i = 0; i < FM; ++i) {
-        acc[i][j] = mfma16<true>(bh, ah[i], acc[i][j]);
-        acc[i][j] = mfma16<true>(bl, ah[i], acc[i][j]);
-        acc[i][j] = mfma16<true>(bh, al[i], acc[i][j]);
-      }
-    }
-  };
-  // OVL: K-tile (sta, stw) multiplied with the next K-tile's split woven in: all fragment reads first, then after
-  // every other MFMA triple one pack2 (two values) of the split -- fenced (sched_barrier) so the compiler keeps the
-  // weave instead of clustering the MFMAs -- and the stash's LDS stores last
+  // K-tile (sta, stw) multiplied with the next K-tile's split woven in: all fragment reads first, then after
+  // every MFMA triple (BN 128: every other) one pack2 (two values) of the split -- fenced (sched_barrier) so the
+  // compiler keeps the weave instead of clustering the MFMAs -- and the stash's LDS stores last
   auto compute_split = [&](int sta, int stw, const DeepRegs& rr, int st) {
     const int c = lane >> 4;
     bf16x8 ah[FM], al[FM], bh[FN], bl[FN];
@@ -1106,8 +1044,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
       bh[j] = *reinterpret_cast<const bf16x8*>(&sW[stw][0][cswz(row, c)]);
       bl[j] = *reinterpret_cast<const bf16x8*>(&sW[stw][1][cswz(row, c)]);
     }
-    uint32_t hw[4 * SL], lw[4 * SL];
-    constexpr int NP = 4 * SL, NT = FM * FN, EVERY = NT / NP > 0 ? NT / NP : 1;
+    uint32_t hw[4], lw[4];
+    constexpr int NP = 4, NT = FM * FN, EVERY = NT / NP;
+    static_assert(NT == NP * EVERY, "every pack2 has its MFMA triple");
     int p = 0;
 #pragma unroll
     for (int j = 0; j < FN; ++j)
@@ -1120,7 +1059,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
         acc[i][j] = mfma16<true>(bh[j], al[i], acc[i][j]);
         asm volatile("" : "+v"(acc[i][j]));
         __builtin_amdgcn_sched_barrier(0);
-        if ((j * FM + i) % EVERY == EVERY - 1 && p < NP) {
+        if ((j * FM + i) % EVERY == EVERY - 1) {
           const f32x4& x = rr.a[p >> 1];
           float x0 = x[(p & 1) * 2], x1 = x[(p & 1) * 2 + 1];
           asm volatile("" : "+v"(x0), "+v"(x1));
@@ -1130,21 +1069,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-#pragma unroll
-    for (; p < NP; ++p) {
-      const f32x4& x = rr.a[p >> 1];
-      pack2(x[(p & 1) * 2], x[(p & 1) * 2 + 1], hw[p], lw[p]);
-    }
-#pragma unroll
-    for (int sl = 0; sl < SL; ++sl) {
-      const int ar = (t >> 2) + 128 * sl;
-      *reinterpret_cast<uint4*>(&sA[st][0][cswz(ar, ac)]) =
-          make_uint4(hw[4 * sl], hw[4 * sl + 1], hw[4 * sl + 2], hw[4 * sl + 3]);
-      *reinterpret_cast<uint4*>(&sA[st][1][cswz(ar, ac)]) =
-          make_uint4(lw[4 * sl], lw[4 * sl + 1], lw[4 * sl + 2], lw[4 * sl + 3]);
-    }
+    const int ar = t >> 2;
+    *reinterpret_cast<uint4*>(&sA[st][0][cswz(ar, ac)]) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
+    *reinterpret_cast<uint4*>(&sA[st][1][cswz(ar, ac)]) = make_uint4(lw[0], lw[1], lw[2], lw[3]);
   };
-  using CA = std::integral_constant<int, WAIT_A>;
 
   // prologue: the loads of steps -NR .. -1 (W(j + 2) where j + 2 >= 0, A(j + NR)), so the steady-state counts hold
   // from step 0 on
@@ -1153,58 +1081,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
     if (j + 2 >= 0) load_w(j + 2, j + 2);
     load_a(j + NR, r[j + NR]);
   }
-  const unsigned long long ts0 = CSTAMP_T();
-  wait_set(r[0], CA{});
+  wait_set(r[0], std::integral_constant<int, WAIT_A>{});
   stash(r[0], 0);
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT_W) : "memory");
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  unsigned long long tsl = CSTAMP_T(), sum_issue = 0, sum_mma = 0, sum_awt = 0, sum_stash = 0, sum_bar = 0;
-  const unsigned long long ts1 = tsl;
   for (int i0 = 0; i0 < nt; i0 += 6) {
 #pragma unroll
     for (int u = 0; u < 6; ++u) {
       const int j = i0 + u;
       if (j >= nt) break;
-      unsigned long long tq, tc;
-      if constexpr (OVL) {
-        wait_set(r[(u + 1) % NR], std::integral_constant<int, WAIT_AE>{});
-        tq = CSTAMP_T();
-        sum_awt += tq - tsl;
-        load_w(j + 2, (u + 2) % 3);
-        load_a(j + NR, r[u % NR]);
-        tc = CSTAMP_T();
-        sum_issue += tc - tq;
-        compute_split(u & 1, u % 3, r[(u + 1) % NR], (u + 1) & 1);
-#if defined(CONV_STAMPS)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-        tq = CSTAMP_T();
-        sum_mma += tq - tc;
-        tc = tq;
-      } else {
-        load_w(j + 2, (u + 2) % 3);
-        load_a(j + NR, r[u % NR]);
-        tq = CSTAMP_T();
-        sum_issue += tq - tsl;
-        compute(u & 1, u % 3);
-#if defined(CONV_STAMPS)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-        tc = CSTAMP_T();
-        sum_mma += tc - tq;
-        wait_set(r[(u + 1) % NR], CA{});
-        tq = CSTAMP_T();
-        sum_awt += tq - tc;
-        stash(r[(u + 1) % NR], (u + 1) & 1);
-        tc = CSTAMP_T();
-        sum_stash += tc - tq;
-      }
+      wait_set(r[(u + 1) % NR], std::integral_constant<int, WAIT_AE>{});
+      load_w(j + 2, (u + 2) % 3);
+      load_a(j + NR, r[u % NR]);
+      compute_split(u & 1, u % 3, r[(u + 1) % NR], (u + 1) & 1);
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT_W) : "memory");
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-      tsl = CSTAMP_T();
-      sum_bar += tsl - tc;
     }
   }
   // the zero-loads past the slice land before the LDS is left -- and before their registers are reused: the last
@@ -1214,16 +1107,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
   wait_set(r[0], std::integral_constant<int, 0>{});
 #pragma unroll
   for (int k = 1; k < NR; ++k) keep_set(r[k]);
-#if defined(CONV_STAMPS)
-  if (threadIdx.x == 0 && g_conv_stamps) {
-    const size_t bid = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    unsigned long long* o = g_conv_stamps + bid * 8;
-    o[0] = ts1 - ts0; o[1] = sum_issue; o[2] = sum_mma; o[3] = sum_awt; o[4] = sum_stash; o[5] = sum_bar;
-    o[6] = (unsigned long long)nt; o[7] = tsl - ts0;
-  }
-#else
-  (void)ts0; (void)ts1; (void)sum_issue; (void)sum_mma; (void)sum_awt; (void)sum_stash; (void)sum_bar;
-#endif
 
   const int li = lane & 15, lk = lane >> 4;
   if (a.ks > 1) {
@@ -1243,13 +1126,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
     return;
   }
   float ymx;
-  if constexpr (BM == 128) {
-    if (a.staged_epi && (int64_t)M * a.Cout * 4 < ((int64_t)1 << 31)) {
-      ymx = conv_store_tile_staged<FN, BN>(g, acc, inv, reinterpret_cast<float*>(smem_dk), wm, wn, lane, m0, M, n0,
-                                           a.Cout, M);
-      if (g.ymax) fold_max<8>(g.ymax, ymx, blockIdx.x + blockIdx.y * 7 + blockIdx.z * 13, reinterpret_cast<float*>(smem_dk));
-      return;
-    }
+  if (a.staged_epi && (int64_t)M * a.Cout * 4 < ((int64_t)1 << 31)) {
+    ymx = conv_store_tile_staged<FN, BN>(g, acc, inv, reinterpret_cast<float*>(smem_dk), wm, wn, lane, m0, M, n0,
+                                         a.Cout, M);
+    if (g.ymax) fold_max<8>(g.ymax, ymx, blockIdx.x + blockIdx.y * 7 + blockIdx.z * 13, reinterpret_cast<float*>(smem_dk));
+    return;
   }
   int64_t mo[FM];
   bool mv[FM];
@@ -1273,7 +1154,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(BM == 128 ?
 // are bank-conflict-free for any start pixel (exhaustive check over start offsets; a tile row that wraps to the next
 // image row costs at most one 2-way conflict).  K order: chunk-major, tap-minor (the weights' K-tile tap * Cin / 32 +
 // chunk); split-K slices take ranges of chunks.  Same products as conv_f16x3_kernel, summed in a different fp32 order.
-constexpr int kPatchMaxPx = 384, kPatchNPL = 6;   // patch pixels (48 KB of fp16 halves), float4 loads per thread
+constexpr int kPatchNPL = kPatchMaxPx * 8 / 512;   // float4 loads per thread (kPatchMaxPx pixels x 32 channels)
 template <int BN>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void conv3x3_patch_f16x3_kernel(
     const ConvF16Args a, int tiles_per_img, int patch_px) {
@@ -1515,117 +1396,84 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvF16Ar
   if (g.ymax) fold_max<4>(g.ymax, ymx, blockIdx.x, wmax);
 }
 
-// K slices for a launch of `tiles` output tiles over nk K-tiles, when the tiles alone leave the GPU's 256 CUs
-// under-filled: the split whose last round of workgroups (over kSlots slots) is fullest (ties: the fewest
-// slices), at least 8 K-tiles per slice.  256 slots (one workgroup per CU) measured +1 % over 512 and level
-// with no split at all once the two backbones share a launch (profiles/r03_ab_conv_slots.txt)
-int conv_pick_ks(int64_t tiles, int nk) {
-  // slots: 256 (one workgroup per CU): a launch with a workgroup for every CU is not split.  (Round 3 counted the
-  // long-K layers -- >= 72 K-tiles: layer3's 3 x 3 convs and the clf conv -- two per CU, splitting them 4 ways at 32
-  // images; with the patch kernel's tiles over the flattened batch, 324 tiles, no split measured +0.3 % on the mfDiMP
-  // line and drops the 7 slice-reduce launches of a step, tools/runs_r4/r4_run19.sh.  Small batches still split.)
-  // The clf conv's K (288 K-tiles) is long enough that two slices per CU still pay: 512 slots from 144 K-tiles
-  // (unsplit 324 us against 254 + 14 us, r4_run20).
-  static const int64_t kSlotsEnv = getenv("MMT_CONV_SLOTS") ? atoi(getenv("MMT_CONV_SLOTS")) : 0;   // tuning
-  const int64_t kSlots = kSlotsEnv > 0 ? kSlotsEnv : (nk >= 144 ? 512 : 256);
-  static const bool nosplit = getenv("MMT_CONV_NOSPLIT") != nullptr;   // batch-invariant summation order
-  if (tiles >= kSlots || nosplit) return 1;
-  int best = 1;
-  double best_eff = 0.0;
-  for (int ks = 1; ks <= kMaxSplitK && nk / ks >= 8; ++ks) {
-    const int64_t w = tiles * ks, rounds = (w + kSlots - 1) / kSlots;
-    const double eff = (double)w / (double)(rounds * kSlots);
-    if (eff > best_eff + 0.02) {
-      best_eff = eff;
-      best = ks;
-    }
-  }
-  return best;
-}
-
 }  // namespace mmt
 
 using namespace mmt;
 
 namespace {
 
-int conv_shape(int N, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad, int& Ho, int& Wo, int& K) {
-  const bool stem = Cin == 3 || Cin == 4;   // 4: a 3-channel image padded with a zero channel
-  if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cout % 64 || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 ||
-      (!stem && Cin % 32))
-    return MMT_E_ARG;
-  K = stem ? kh * kw * 4 : kh * kw * Cin;
-  Ho = (H + 2 * pad - kh) / stride + 1;
-  Wo = (W + 2 * pad - kw) / stride + 1;
-  if (Ho <= 0 || Wo <= 0) return MMT_E_ARG;
-  const int64_t M = (int64_t)N * Ho * Wo;
-  if (M > (int64_t)1 << 30 || (int64_t)Cout * K > (int64_t)1 << 30) return MMT_E_ARG;
-  return MMT_OK;
+const ConvKnobs& conv_knobs() {
+  static const ConvKnobs k = conv_knobs_from_env();   // once per process
+  return k;
 }
 
-// output channels per tile: 128 where the 128-wide tiles fill the GPU (or everywhere but the stem by default);
-// MMT_CONV_PREFER64 (tuning): 64-wide tiles instead of splitting K when the 128-wide ones leave it under-filled
-int conv_bn(int64_t gm, int Cin, int Cout, int G) {
-  static const bool prefer64 = getenv("MMT_CONV_PREFER64") != nullptr;
-  if (Cin <= 4 || Cout % 128) return 64;
-  if (prefer64 && gm * (Cout / 128) * G < 512) return 64;
-  return 128;
-}
-
-// the 3 x 3 / stride-1 patch kernel's geometry: *tiles = the launch's tiles, *tiles_per_img = tiles per image (128
-// raster pixels each) or 0 for tiles over the flattened batch (chosen when the images' partial last tiles would waste
-// more than 4 % of the rows and every batch tile's patch fits -- HW >= 128, so a tile spans at most two images);
-// returns the largest tile's patch (pixels), 0 when the shape is not one it runs
-int patch_plan(int N, int H, int W, int Cin, int kh, int kw, int stride, int pad, int* tiles, int* tiles_per_img) {
-  static const bool off = getenv("MMT_CONV_NOPATCH") != nullptr;   // tuning A/B: the generic kernel
-  static const bool per_img = getenv("MMT_CONV_PATCH_PERIMG") != nullptr;   // tuning A/B: per-image tiles only
-  if (off || kh != 3 || kw != 3 || stride != 1 || pad != 1 || Cin % 32 || Cin < 32) return 0;
-  const int HW = H * W, tpi = (HW + 127) / 128, PW = W + 2;
-  int px = 0;
-  for (int tl = 0; tl < tpi; ++tl) {
-    const int o0 = tl * 128, o1 = std::min(o0 + 128, HW);
-    px = std::max(px, ((o1 - 1) / W - o0 / W + 3) * PW);
+// the pointers and flags of a launch's groups, checked and copied into a; ds: the fused downsamples' second sources
+// (such a launch takes no residual and is not the pooled stem)
+bool conv_groups(ConvF16Args& a, const mmt_conv_group* groups, const mmt_conv_ds* ds, int G) {
+  if (!groups || G < 1 || G > kMaxGroups) return false;
+  const int allowed = MMT_CONV_RELU | MMT_CONV_MAX | (ds ? 0 : MMT_CONV_POOL);
+  for (int i = 0; i < G; ++i) {
+    const mmt_conv_group& c = groups[i];
+    if (!c.x || !c.w_hi || !c.w_lo || !c.y || !(c.w_scale > 0) || (c.flags & ~allowed) || (!c.x_max && !(c.x_scale > 0)) ||
+        (c.flags & MMT_CONV_POOL) != (groups[0].flags & MMT_CONV_POOL) ||
+        // the pooled stem kernel neither max-merges nor adds a residual: refuse operands it would drop
+        ((c.flags & MMT_CONV_POOL) && ((c.flags & MMT_CONV_MAX) || c.resid)) ||
+        (ds && (c.resid || !ds[i].x2 || (!ds[i].x2_max && !(ds[i].x2_scale > 0)))))
+      return false;
+    a.g[i] = ConvGroupArgs{c.x, c.w_hi, c.w_lo, c.bias, c.resid, c.y, c.x_max, c.y_max, c.x_scale, 1.0f / c.w_scale,
+                           c.flags, ds ? ds[i].x2 : nullptr, ds ? ds[i].x2_max : nullptr, ds ? ds[i].x2_scale : 0.f};
   }
-  const int64_t total = (int64_t)N * HW, gtiles = (total + 127) / 128;
-  if (!per_img && HW >= 128 && (int64_t)N * tpi * 128 > total * 104 / 100 && N > 1) {
-    int gpx = 0;
-    for (int64_t tl = 0; tl < gtiles; ++tl) {
-      const int64_t g0 = tl * 128, gend = std::min(g0 + 128, total);
-      const int64_t nA = g0 / HW, y0 = (g0 - nA * HW) / W;
-      const int64_t aend = std::min(gend, (nA + 1) * HW) - nA * HW;
-      int rows = (int)((aend - 1) / W - y0 + 3);
-      if (gend > (nA + 1) * HW) rows += (int)((gend - (nA + 1) * HW - 1) / W + 3);
-      gpx = std::max(gpx, rows * PW);
-    }
-    if (gpx <= kPatchMaxPx) {
-      *tiles = (int)gtiles;
-      *tiles_per_img = 0;
-      return gpx;
-    }
+  // the twin layers of a grouped launch write disjoint outputs unless they merge (a MAX layer reads y)
+  return !(G == 2 && (a.g[0].y == a.g[1].y || (a.g[0].flags | a.g[1].flags) & MMT_CONV_MAX));
+}
+
+// the plan's one launch, then the split-K reduce
+int launch_plan(const ConvPlan& p, ConvF16Args& a, const ConvProblem& q, void* ws, hipStream_t s) {
+  a.N = q.N; a.H = q.H; a.W = q.W; a.Cin = q.Cin; a.Cout = q.Cout; a.kh = q.kh; a.kw = q.kw; a.stride = q.stride;
+  a.pad = q.pad; a.Ho = p.Ho; a.Wo = p.Wo; a.Kp = q.Kp; a.ks = p.ks;
+  a.Cin2 = q.Cin2; a.H2 = q.H2; a.W2 = q.W2; a.stride2 = q.stride2;
+  a.part = static_cast<float*>(ws);
+  a.xcd_order = a.staged_epi = 1;
+  const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(512);
+  const bool wide = p.bn == 128;
+  switch (p.kernel) {
+    case ConvKernel::STEM_POOL:
+      hipLaunchKernelGGL(conv_stem_pool_f16x3_kernel, grid, block, 0, s, a, p.PHo, p.PWo);
+      break;
+    case ConvKernel::PATCH:
+      if (wide) hipLaunchKernelGGL(conv3x3_patch_f16x3_kernel<128>, grid, block, p.lds_bytes, s, a, p.tiles_per_img, p.patch_px);
+      else hipLaunchKernelGGL(conv3x3_patch_f16x3_kernel<64>, grid, block, p.lds_bytes, s, a, p.tiles_per_img, p.patch_px);
+      break;
+    case ConvKernel::STEM:
+      hipLaunchKernelGGL(conv_stem_f16x3_kernel, grid, block, 0, s, a);
+      break;
+    case ConvKernel::GENERIC:
+      if (q.Cin <= 4) hipLaunchKernelGGL((conv_f16x3_kernel<64, true>), grid, block, 0, s, a);
+      else if (wide) hipLaunchKernelGGL((conv_f16x3_kernel<128, false>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((conv_f16x3_kernel<64, false>), grid, block, 0, s, a);
+      break;
+    case ConvKernel::DEEP:
+      if (wide) hipLaunchKernelGGL(conv_f16x3_deep_kernel<128>, grid, block, 0, s, a);
+      else hipLaunchKernelGGL(conv_f16x3_deep_kernel<64>, grid, block, 0, s, a);
+      break;
+    case ConvKernel::NONE:
+      return MMT_E_ARG;
   }
-  if (px > kPatchMaxPx) return 0;
-  *tiles = N * tpi;
-  *tiles_per_img = tpi;
-  return px;
+  if (p.reduce) {
+    const int64_t n4 = (int64_t)q.N * p.Ho * p.Wo * q.Cout / 4;
+    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256), q.G), dim3(256), 0, s, a);
+  }
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
 }
 
-// output pixels per tile of the generic kernel: 128, or 256 with MMT_CONV_BM=256 (tuning) for 128-wide tiles
-int conv_bm_for(int Cin, int bn) {
-  static const bool old = getenv("MMT_CONV_OLD") != nullptr;
-  static const int bm = getenv("MMT_CONV_BM") ? atoi(getenv("MMT_CONV_BM")) : 128;
-  return bm == 256 && !old && Cin > 4 && bn == 128 ? 256 : 128;
-}
-
-// M tiles of a launch (the patch kernel tiles each image separately) and its K split
-int64_t conv_ks_for(int N, int H, int W, int Ho, int Wo, int Cin, int Cout, int kh, int kw, int stride, int pad, int Kp,
-                    int G) {
-  const int64_t M = (int64_t)N * Ho * Wo;
-  const int bn = conv_bn((M + 127) / 128, Cin, Cout, G);
-  int ptiles = 0, tpi = 0;
-  if (patch_plan(N, H, W, Cin, kh, kw, stride, pad, &ptiles, &tpi))
-    return std::min<int64_t>(conv_pick_ks((int64_t)ptiles * (Cout / bn) * G, Kp / 32), Cin / 32);
-  const int bm = conv_bm_for(Cin, bn);
-  return conv_pick_ks((M + bm - 1) / bm * (Cout / bn) * G, Kp / 32);
+int conv_launch(const mmt_conv_group* groups, const mmt_conv_ds* ds, ConvProblem q, void* ws, size_t ws_bytes,
+                void* stream) {
+  ConvF16Args a{};
+  if (!conv_groups(a, groups, ds, q.G)) return MMT_E_ARG;
+  q.pool = groups[0].flags & MMT_CONV_POOL;
+  q.ws_bytes = ws ? ws_bytes : 0;
+  const ConvPlan p = conv_plan(q, conv_knobs());
+  return p.error ? MMT_E_ARG : launch_plan(p, a, q, ws, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -1636,194 +1484,22 @@ size_t mmt_conv_max_words(void) { return (size_t)kMaxShards * kShardStride; }
 
 size_t mmt_conv2d_f16x3_ws_bytes(int N, int H, int W, int Cin, int Cout, int kh, int kw, int stride, int pad,
                                  int groups) {
-  int Ho, Wo, K;
-  if (groups < 1 || groups > kMaxGroups || conv_shape(N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, K) != MMT_OK)
-    return 0;
-  const int Kp = (K + 31) / 32 * 32;
-  const int64_t ks = conv_ks_for(N, H, W, Ho, Wo, Cin, Cout, kh, kw, stride, pad, Kp, groups);
-  return ks > 1 ? (size_t)(ks * groups * N * Ho * Wo * (int64_t)Cout * 4) : 0;
+  const ConvProblem q{N, H, W, Cin, Cout, kh, kw, stride, pad, (int)conv_kp(Cin, kh, kw), groups, false, 0, 0, 0, 0, SIZE_MAX};
+  return conv_plan(q, conv_knobs()).ws_needed;   // (0 for a rejected shape)
 }
 
 int mmt_conv2d_f16x3_groups(const mmt_conv_group* groups, int G, int N, int H, int W, int Cin, int Kp, int Cout,
                             int kh, int kw, int stride, int pad, void* ws, size_t ws_bytes, void* stream) {
-  int Ho, Wo, K;
-  if (!groups || G < 1 || G > kMaxGroups || conv_shape(N, H, W, Cin, Cout, kh, kw, stride, pad, Ho, Wo, K) != MMT_OK ||
-      Kp != (K + 31) / 32 * 32)
-    return MMT_E_ARG;
-  ConvF16Args a{};
-  for (int i = 0; i < G; ++i) {
-    const mmt_conv_group& c = groups[i];
-    if (!c.x || !c.w_hi || !c.w_lo || !c.y || !(c.w_scale > 0) ||
-        (c.flags & ~(MMT_CONV_RELU | MMT_CONV_MAX | MMT_CONV_POOL)) || (!c.x_max && !(c.x_scale > 0)) ||
-        (c.flags & MMT_CONV_POOL) != (groups[0].flags & MMT_CONV_POOL) ||
-        // the pooled stem kernel neither max-merges nor adds a residual: refuse operands it would drop
-        ((c.flags & MMT_CONV_POOL) && ((c.flags & MMT_CONV_MAX) || c.resid)))
-      return MMT_E_ARG;
-    a.g[i] = ConvGroupArgs{c.x, c.w_hi, c.w_lo, c.bias, c.resid, c.y, c.x_max, c.y_max, c.x_scale, 1.0f / c.w_scale,
-                           c.flags, nullptr, nullptr, 0.f};
-  }
-  // the twin layers of a grouped launch write disjoint outputs unless they merge (a MAX layer reads y)
-  if (G == 2 && (a.g[0].y == a.g[1].y || (a.g[0].flags | a.g[1].flags) & MMT_CONV_MAX)) return MMT_E_ARG;
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad;
-  a.Ho = Ho; a.Wo = Wo; a.Kp = Kp;
-  const int64_t M = (int64_t)N * Ho * Wo;
-  const hipStream_t s = (hipStream_t)stream;
-  if (groups[0].flags & MMT_CONV_POOL) {
-    // the 7 x 7 / stride-2 stem with the 3 x 3 / stride-2 / pad-1 max-pool fused; y is the pooled map
-    if (Cin != 4 || Cout != 64 || kh != 7 || kw != 7 || stride != 2 || Kp != 224)
-      return MMT_E_ARG;
-    const int PHo = (Ho - 1) / 2 + 1, PWo = (Wo - 1) / 2 + 1;
-    const unsigned tiles = (unsigned)(N * ((PHo + kPoolT - 1) / kPoolT) * ((PWo + kPoolT - 1) / kPoolT));
-    a.ks = 1;
-    hipLaunchKernelGGL(conv_stem_pool_f16x3_kernel, dim3(tiles, 1, G), dim3(512), 0, s, a, PHo, PWo);
-    return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
-  }
-  int ks = (int)conv_ks_for(N, H, W, Ho, Wo, Cin, Cout, kh, kw, stride, pad, Kp, G);
-  if (ks > 1 && (!ws || ws_bytes < (size_t)(ks * G * M * (int64_t)Cout * 4))) ks = 1;
-  a.ks = ks;
-  a.part = static_cast<float*>(ws);
-  const int bn = conv_bn((M + 127) / 128, Cin, Cout, G);
-  const int conv_bm = conv_bm_for(Cin, bn);
-  const unsigned gm = (unsigned)((M + conv_bm - 1) / conv_bm);
-  const dim3 grid(gm, Cout / bn, G * ks);
-  const dim3 dgrid(gm * (Cout / bn), 1, G * ks);   // the deep kernel: M x N tiles flattened
-  static const int xcd_env = getenv("MMT_CONV_XCD") ? atoi(getenv("MMT_CONV_XCD")) : -1;   // tuning: 0 / 1 force
-  a.xcd_order = xcd_env != 0;
-  // the LDS-staged conv epilogue (mfDiMP 7 396 -> 7 531 frames/s, profiles/r05_ab_conv_staged_epilogue.txt;
-  // MMT_CONV_STAGED=0, tuning: fragment-shaped stores)
-  static const bool staged_env = !getenv("MMT_CONV_STAGED") || atoi(getenv("MMT_CONV_STAGED")) != 0;
-  a.staged_epi = staged_env ? 1 : 0;
-  // the stem on a 4-channel image: 2-D tiles from an LDS input patch (MMT_CONV_STEM_OLD: the gather kernel, tuning)
-  static const bool stem_old = getenv("MMT_CONV_STEM_OLD") != nullptr;
-  static const int stem_th = getenv("MMT_CONV_STEM_TH") ? atoi(getenv("MMT_CONV_STEM_TH")) : 16;   // tuning: 8
-  static const bool conv_old = getenv("MMT_CONV_OLD") != nullptr;   // tuning: conv_f16x3_kernel (two-deep)
-  static const int conv_nr = getenv("MMT_CONV_NR") ? atoi(getenv("MMT_CONV_NR")) : 2;   // tuning: 3
-  // the next K-tile's split woven into the MFMAs (+1 % on the mfDiMP line, tools/runs_r4/r4_run8.sh); MMT_CONV_OVL=0
-  // (tuning): the split after them
-  static const bool conv_ovl = !getenv("MMT_CONV_OVL") || atoi(getenv("MMT_CONV_OVL")) != 0;
-  int ptiles = 0, tpi = 0;
-  const int ppx = patch_plan(N, H, W, Cin, kh, kw, stride, pad, &ptiles, &tpi);
-  if (ppx) {
-    const dim3 pgrid((unsigned)ptiles, Cout / bn, G * ks);
-    const size_t lds = (size_t)(2 * kPatchMaxPx * 32 + 2 * 2 * bn * 32) * 2;   // 80 KB (BN 128): two per CU
-    if (bn == 128)
-      hipLaunchKernelGGL(conv3x3_patch_f16x3_kernel<128>, pgrid, dim3(512), lds, s, a, tpi, ppx);
-    else
-      hipLaunchKernelGGL(conv3x3_patch_f16x3_kernel<64>, pgrid, dim3(512), lds, s, a, tpi, ppx);
-  } else if (!stem_old && Cin == 4 && Cout == 64 && ks == 1 && kh <= 7 && kw <= 7 && stride <= 2 && Kp / 32 <= kStemMaxKt) {
-    const int th = stem_th == 8 ? 8 : 16;
-    const unsigned tiles = (unsigned)(((Ho + th - 1) / th) * ((Wo + kStemTW - 1) / kStemTW) * N);
-    if (th == 8)
-      hipLaunchKernelGGL(conv_stem_f16x3_kernel<8>, dim3(tiles, 1, G), dim3(512), 0, s, a);
-    else
-      hipLaunchKernelGGL(conv_stem_f16x3_kernel<16>, dim3(tiles, 1, G), dim3(512), 0, s, a);
-  } else if (Cin <= 4)
-    hipLaunchKernelGGL((conv_f16x3_kernel<64, true>), grid, dim3(512), 0, s, a);
-  else if (conv_old) {   // tuning A/B: the two-deep pipeline
-    if (bn == 128)
-      hipLaunchKernelGGL((conv_f16x3_kernel<128, false>), grid, dim3(512), 0, s, a);
-    else
-      hipLaunchKernelGGL((conv_f16x3_kernel<64, false>), grid, dim3(512), 0, s, a);
-  } else if (conv_bm == 256) {
-    hipLaunchKernelGGL((conv_f16x3_deep_kernel<128, 2, 256>), dgrid, dim3(512), 0, s, a);
-  } else if (conv_ovl) {
-    if (bn == 128)
-      hipLaunchKernelGGL((conv_f16x3_deep_kernel<128, 3, 128, true>), dgrid, dim3(512), 0, s, a);
-    else
-      hipLaunchKernelGGL((conv_f16x3_deep_kernel<64, 3, 128, true>), dgrid, dim3(512), 0, s, a);
-  } else if (conv_nr == 2) {
-    if (bn == 128)
-      hipLaunchKernelGGL((conv_f16x3_deep_kernel<128, 2>), dgrid, dim3(512), 0, s, a);
-    else
-      hipLaunchKernelGGL((conv_f16x3_deep_kernel<64, 2>), dgrid, dim3(512), 0, s, a);
-  } else {
-    if (bn == 128)
-      hipLaunchKernelGGL((conv_f16x3_deep_kernel<128, 3>), dgrid, dim3(512), 0, s, a);
-    else
-      hipLaunchKernelGGL((conv_f16x3_deep_kernel<64, 3>), dgrid, dim3(512), 0, s, a);
-  }
-#if defined(CONV_STAMPS)
-  if (!ppx && !conv_old && Cin > 4 && conv_bm == 128) {   // the deep kernel ran: per-phase cycles averaged over its workgroups
-    const size_t nb = (size_t)dgrid.x * dgrid.y * dgrid.z;
-    unsigned long long* buf = nullptr;
-    if (hipMalloc(&buf, nb * 64) == hipSuccess) {
-      hipMemsetAsync(buf, 0, nb * 64, s);
-      hipMemcpyToSymbolAsync(HIP_SYMBOL(g_conv_stamps), &buf, sizeof(buf), 0, hipMemcpyHostToDevice, s);
-      if (conv_ovl)
-        hipLaunchKernelGGL((conv_f16x3_deep_kernel<128, 3, 128, true>), dgrid, dim3(512), 0, s, a);
-      else if (conv_nr == 2)
-        hipLaunchKernelGGL((conv_f16x3_deep_kernel<128, 2>), dgrid, dim3(512), 0, s, a);
-      hipStreamSynchronize(s);
-      std::vector<unsigned long long> h(nb * 8);
-      hipMemcpy(h.data(), buf, nb * 64, hipMemcpyDeviceToHost);
-      double acc[8] = {0};
-      for (size_t b = 0; b < nb; ++b)
-        for (int k = 0; k < 8; ++k) acc[k] += (double)h[b * 8 + k];
-      const double kt = acc[6] > 0 ? acc[6] : 1;
-      fprintf(stderr, "conv stamps M=%lld Cin=%d Cout=%d k=%d: per K-tile cycles issue %.0f mfma %.0f a-wait %.0f stash %.0f "
-              "w-wait+barrier %.0f | prologue %.0f, total/K-tile %.0f (%zu blocks)\n", (long long)M, Cin, Cout, kh,
-              acc[1] / kt, acc[2] / kt, acc[3] / kt, acc[4] / kt, acc[5] / kt, acc[0] / nb, acc[7] / kt, nb);
-      const unsigned long long* z = nullptr;
-      hipMemcpyToSymbol(HIP_SYMBOL(g_conv_stamps), &z, sizeof(z));
-      hipFree(buf);
-    }
-  }
-#endif
-  if (ks > 1) {
-    const int64_t q = M * Cout / 4;
-    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((q + 255) / 256), G), dim3(256), 0, s, a);
-  }
-  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+  return conv_launch(groups, nullptr, ConvProblem{N, H, W, Cin, Cout, kh, kw, stride, pad, Kp, G, false, 0, 0, 0, 0, 0}, ws,
+                     ws_bytes, stream);
 }
 
 int mmt_conv2d_f16x3_ds_groups(const mmt_conv_group* groups, const mmt_conv_ds* ds, int G, int N, int H, int W,
                                int Cin, int H2, int W2, int Cin2, int stride2, int Kp, int Cout, void* ws,
                                size_t ws_bytes, void* stream) {
-  int Ho, Wo, K;
-  // conv3 is 1 x 1 / stride 1 over [N][H][W][Cin]; the downsample 1 x 1 / stride2 over [N][H2][W2][Cin2] lands on
-  // the same H x W grid; the weights hold both K ranges
-  if (!groups || !ds || G < 1 || G > kMaxGroups || Cin < 32 || Cin % 32 || Cin2 < 32 || Cin2 % 32 || stride2 < 1 ||
-      H2 <= 0 || W2 <= 0 || (H2 - 1) / stride2 + 1 != H || (W2 - 1) / stride2 + 1 != W || Kp != Cin + Cin2 ||
-      conv_shape(N, H, W, Kp, Cout, 1, 1, 1, 0, Ho, Wo, K) != MMT_OK ||
-      (int64_t)N * H2 * W2 * Cin2 > ((int64_t)1 << 29))   // 32-bit buffer offsets into x2
-    return MMT_E_ARG;
-  ConvF16Args a{};
-  for (int i = 0; i < G; ++i) {
-    const mmt_conv_group& c = groups[i];
-    if (!c.x || !c.w_hi || !c.w_lo || !c.y || !(c.w_scale > 0) || c.resid ||
-        (c.flags & ~(MMT_CONV_RELU | MMT_CONV_MAX)) || (!c.x_max && !(c.x_scale > 0)) || !ds[i].x2 ||
-        (!ds[i].x2_max && !(ds[i].x2_scale > 0)))
-      return MMT_E_ARG;
-    a.g[i] = ConvGroupArgs{c.x, c.w_hi, c.w_lo, c.bias, nullptr, c.y, c.x_max, c.y_max, c.x_scale, 1.0f / c.w_scale,
-                           c.flags, ds[i].x2, ds[i].x2_max, ds[i].x2_scale};
-  }
-  if (G == 2 && (a.g[0].y == a.g[1].y || (a.g[0].flags | a.g[1].flags) & MMT_CONV_MAX)) return MMT_E_ARG;
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.kh = 1; a.kw = 1; a.stride = 1; a.pad = 0;
-  a.Ho = H; a.Wo = W; a.Kp = Kp;
-  a.Cin2 = Cin2; a.H2 = H2; a.W2 = W2; a.stride2 = stride2;
-  const int64_t M = (int64_t)N * H * W;
-  int ks = (int)conv_ks_for(N, H, W, H, W, Kp, Cout, 1, 1, 1, 0, Kp, G);
-  if (ks > 1 && (!ws || ws_bytes < (size_t)(ks * G * M * (int64_t)Cout * 4))) ks = 1;
-  a.ks = ks;
-  a.part = static_cast<float*>(ws);
-  static const int xcd_env = getenv("MMT_CONV_XCD") ? atoi(getenv("MMT_CONV_XCD")) : -1;
-  a.xcd_order = xcd_env != 0;
-  // the LDS-staged conv epilogue (mfDiMP 7 396 -> 7 531 frames/s, profiles/r05_ab_conv_staged_epilogue.txt;
-  // MMT_CONV_STAGED=0, tuning: fragment-shaped stores)
-  static const bool staged_env = !getenv("MMT_CONV_STAGED") || atoi(getenv("MMT_CONV_STAGED")) != 0;
-  a.staged_epi = staged_env ? 1 : 0;
-  const int bn = conv_bn((M + 127) / 128, Kp, Cout, G);
-  const dim3 dgrid((unsigned)((M + 127) / 128 * (Cout / bn)), 1, G * ks);
-  const hipStream_t s = (hipStream_t)stream;
-  if (bn == 128)
-    hipLaunchKernelGGL((conv_f16x3_deep_kernel<128, 3, 128, true>), dgrid, dim3(512), 0, s, a);
-  else
-    hipLaunchKernelGGL((conv_f16x3_deep_kernel<64, 3, 128, true>), dgrid, dim3(512), 0, s, a);
-  if (ks > 1) {
-    const int64_t q = M * Cout / 4;
-    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((q + 255) / 256), G), dim3(256), 0, s, a);
-  }
-  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+  if (!ds || Cin2 <= 0) return MMT_E_ARG;   // (Cin2 > 0 is what tells the planner of the second source)
+  return conv_launch(groups, ds, ConvProblem{N, H, W, Cin, Cout, 1, 1, 1, 0, Kp, G, false, Cin2, H2, W2, stride2, 0}, ws,
+                     ws_bytes, stream);
 }
 
 int mmt_conv2d_f16x3(const float* x, int N, int H, int W, int Cin, const uint16_t* w_hi, const uint16_t* w_lo,

@@ -556,10 +556,9 @@ int mmt_conv2d_f32_ld(const float* x, int N, int H, int W, int Cin, int ldx, con
   // the float4 operand loads of the FAST kernels need 16-B aligned pixel rows (a group's channel offset included)
   const bool vec = ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   // 32-deep K-tiles (half the barriers per MFMA) where a tile stays inside one tap; 16 for Cin = 48 / 16
-  static const int bk = getenv("MMT_CONV_BK") ? atoi(getenv("MMT_CONV_BK")) : 32;
   if (flags & MMT_CONV_W4)
     hipLaunchKernelGGL((conv_f32_kernel<false, 16, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
-  else if (vec && Cin % 32 == 0 && bk == 32)
+  else if (vec && Cin % 32 == 0)
     hipLaunchKernelGGL((conv_f32_kernel<true, 32>), grid, dim3(256), 0, (hipStream_t)stream, a);
   else if (vec && Cin % 16 == 0)
     hipLaunchKernelGGL((conv_f32_kernel<true, 16>), grid, dim3(256), 0, (hipStream_t)stream, a);

@@ -49,8 +49,9 @@ def test_inline_asm_load_kernels_never_touch_pending_load_registers(tmp_path):
         text = out.read_text()
         for k in _asm_vgpr_load_kernels(text):
             audited[k] = isa_audit.audit(text, k)
-    # the deep conv kernel's instances (the fused-downsample path included) are among them
-    assert sum("conv_f16x3_deep_kernel" in k for k in audited) >= 4, sorted(audited)
+    # the deep conv kernel's two instances (BN 64 / 128; the fused-downsample path is a runtime branch of each) are
+    # among them, and no other
+    assert sum("conv_f16x3_deep_kernel" in k for k in audited) == 2, sorted(audited)
     print(f"{len(audited)} kernels with inline-asm VGPR loads audited")
     bad = {k: v[:3] for k, v in audited.items() if v}
     assert not bad, bad

@@ -1,5 +1,5 @@
-"""f16x3 conv timing on the DiMP feature net's shapes (GPU tuning tool, not a test; the tuning knobs
-MMT_CONV_SLOTS / MMT_CONV_PREFER64 / MMT_CONV_NOSPLIT are read once per process, so one process per setting).
+"""f16x3 conv timing on the DiMP feature net's shapes (GPU tuning tool, not a test; the switches
+MMT_CONV_NOSPLIT / MMT_CONV_NOPATCH / MMT_CONV_OLD are read once per process, so one process per setting).
 Prints one JSON line per shape: microseconds per launch, algorithmic TF/s and the fraction of 833 TF/s."""
 import ctypes
 import json

@@ -1,6 +1,6 @@
 """Diagnostic (tuning tool): the DiMP feature net's layer3 with the fused stem + max-pool against the separate
 max-pool (bitwise), the pooled stem maps of both, and layer3 sums against the reference golden
-(tests/golden/dimpnet_det.npz).  Conv kernel knobs come from the environment (MMT_CONV_*)."""
+(tests/golden/dimpnet_det.npz).  The conv switches come from the environment (MMT_CONV_NOSPLIT / NOPATCH / OLD)."""
 import os
 import sys
 
