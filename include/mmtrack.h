@@ -88,8 +88,10 @@ const char* mmt_version(void);
  * mmt_dimp_optimize_strided (-1 = contiguous stride, 0 = broadcast; the round-3 entry point
  * mmt_dimp_optimize_dev, where 0 meant contiguous, is gone, so an old binding fails to resolve it
  * instead of silently reading sample 0 everywhere).  6: candidate elimination over any template mask
- * (MMT_CE_TEMPLATE_MASK, mmt_set_ce_template_mask, mmt_op_ce_rows / _f16x3, timing class "ce_rows"). */
-#define MMT_ABI_VERSION 6
+ * (MMT_CE_TEMPLATE_MASK, mmt_set_ce_template_mask, mmt_op_ce_rows / _f16x3, timing class "ce_rows").  7: operator entry points of the token kernels
+ * (mmt_op_layernorm_ex, mmt_op_ce_select, mmt_op_final_norm_recover, mmt_op_prompt_reduce,
+ * mmt_op_prompt_expand_ln), mmt_prompt_fold and mmt_tokens_force_config. */
+#define MMT_ABI_VERSION 7
 int mmt_abi_version(void);
 /* pinned host memory that kernels read and write in place (mapped + coherent: a kernel sees the host's latest
  * writes and the host sees the kernel's after an event, with no copy launch) -- the DiMP pool's frame descriptors
@@ -462,6 +464,105 @@ int mmt_op_ce_rows(const void* qkv, int B, int N, int heads, int lens_t, const i
                    const int* nrows, float* ce_prob, void* hip_stream);
 int mmt_op_ce_rows_f16x3(const void* qkv_hi, const void* qkv_lo, int B, int N, int heads, int lens_t, const int* rows,
                          int rows_pitch, const int* nrows, float* ce_prob, float s_qkv, void* hip_stream);
+
+/* ---- token kernels (csrc/tokens.hip): the row kernels between the GEMMs of the ViPT / OSTrack path, rows of 768
+ *      fp32.  Every entry checks its arguments first and returns MMT_E_ARG with nothing launched; index lists
+ *      (gather, gidx, slot2pos) are read back and range-checked, so these calls are synchronous.              */
+/* a residual-stream update left as split-K partial slabs (ws [ks][slab floats], ks in 1..8): the consuming kernel
+ * forms X[row] += ((p0 + p1) + ...) * inv + bias itself, slabs in order.  A NULL struct or ws: nothing pending */
+typedef struct mmt_row_reduce {
+  const float* ws;
+  int ks;
+  int64_t slab;
+  float inv;
+  const float* bias;   /* [768] */
+} mmt_row_reduce;
+/* out[r] = LN(x[src(r)]) (eps 1e-6), src(r) = gather ? (r / rows_per_seq) * in_rows_per_seq + gather[r] : r.
+ * out: bf16, or with out_lo the fp16 hi / lo halves of LN * out_scale; out_f32: the fp32 rows; xcopy[r] = x[src(r)]
+ * (after the pending update, which otherwise is written back to x).  Any output may be NULL, not all.          */
+int mmt_op_layernorm_ex(const float* x, const float* w, const float* b, void* out, void* out_lo, float out_scale,
+                        float* out_f32, int rows, int rows_per_seq, const int* gather, int in_rows_per_seq,
+                        float* xcopy, const mmt_row_reduce* reduce, void* hip_stream);
+/* candidate elimination (attn_blocks.py:37-73) + the LN2 over the survivors.  key = mean over heads of prob
+ * [B][heads][Ls]; order: key descending, ties to the lower index; the first keep stay.  gidx_in [B][Ls] slot id
+ * (< Lx) of each compact search token -> gidx_out [B][keep], gather [B][Lz + keep] (source compact row of each new
+ * row, identity over the template), slot2pos [B][Lx] (new compact position or -1), removed [B][Lx] (the dropped
+ * slot ids in order, from removed_off).  1 <= keep <= Ls <= 1024, heads >= 1.                                  */
+typedef struct mmt_ce_args {
+  int B, Lz, Ls, keep, heads, Lx;
+  const float* prob;
+  const int* gidx_in;
+  int* gidx_out;
+  int* gather;
+  int* slot2pos;
+  int* removed;
+  int removed_off;
+} mmt_ce_args;
+/* fused = 0: the select launch, then mmt_op_layernorm_ex's launch with the gather; fused = 1: the one-launch kernel
+ * (few sequences), MMT_E_STATE with nothing launched where it does not take the batch.  x [B][in_rows_per_seq][768]. */
+int mmt_op_ce_select(const mmt_ce_args* ce, int fused, const float* x, const float* w, const float* b, void* out,
+                     void* out_lo, float out_scale, int in_rows_per_seq, float* xcopy, const mmt_row_reduce* reduce,
+                     void* hip_stream);
+/* final norm + recover_tokens (vit_ce_prompt.py:318-339): feat [B][Lx][768] (bf16, or fp16 halves with feat_lo) =
+ * LN of the search slots' rows of X [B][rows_per_seq][768] by slot2pos, exact zeros at pruned slots (-1);
+ * feat_f32 (or NULL) [B][Lz + Lx][768] also holds the template rows.                                            */
+int mmt_op_final_norm_recover(const float* X, int rows_per_seq, const int* slot2pos, const float* w, const float* b,
+                              int B, int Lz, int Lx, void* feat, void* feat_lo, float feat_scale, float* feat_f32,
+                              const mmt_row_reduce* reduce, void* hip_stream);
+/* Prompt_block up to the fovea (vit_ce_prompt.py:62-68) per slot: a8 / c8 [B][Lz + Lx][8].
+ * layer 0: a8 = conv0_0(LN_A(srcA)), c8 = conv0_1(LN_B(srcB)), srcA / srcB [B][Lz + Lx][768], raw weights.
+ * layer > 0: a8 from the recovered X (srcA [B][srcA_rows][768] by slot2pos, zero row at -1) with w00 / b00 =
+ * mmt_prompt_fold's w00f / b00f; c8 from the previous block's a8p / c8p / smooth_p through fold (its fovea
+ * statistics from fstat_p [B][32] as mmt_op_prompt_expand_ln wrote them, or NULL: reduced here).  Lz + Lx <= 1024. */
+typedef struct mmt_prompt_args {
+  int layer, B, Lz, Lx;
+  const float* srcA;
+  int srcA_rows;
+  const float* srcB;
+  const int* slot2pos;
+  const float *lnA_w, *lnA_b, *lnB_w, *lnB_b;
+  const float *w00, *b00, *w01, *b01;
+  const float* fold;
+  float* a8;
+  float* c8;
+  const float* a8p;
+  const float* c8p;
+  float smooth_p;
+  const float* fstat_p;
+} mmt_prompt_args;
+int mmt_op_prompt_reduce(const mmt_prompt_args* a, const mmt_row_reduce* reduce, void* hip_stream);
+/* the rest of the prompt block fused with the layer's LN1: s8 = fovea(a8) + c8, P = conv1x1(s8) + b1 (w1 channel-
+ * major [8][768]); mode 1: X[r] = (tok_rgb[r] + P[r]) + pos[t]; mode 2: X[r] += P[slot(t)], slot(t) = t < Lz ? t :
+ * Lz + gidx[b][t - Lz]; out = LN(X[r]) (bf16 or fp16 halves); fstat (or NULL) [B][32] the fovea statistics.       */
+typedef struct mmt_ln_prompt_args {
+  int mode, rows, rows_per_seq, Lz, Lx;
+  float* X;
+  const float* a8;
+  const float* c8;
+  float smooth;
+  float* fstat;
+  const float* w1;
+  const float* b1;
+  const float* tok_rgb;
+  const float* pos;
+  const int* gidx;
+  const float* w;
+  const float* b;
+  void* out;
+  void* out_lo;
+  float out_scale;
+} mmt_ln_prompt_args;
+int mmt_op_prompt_expand_ln(const mmt_ln_prompt_args* a, void* hip_stream);
+/* the weight loader's folds for deep prompt layer i, on the host (no GPU): w00f [8][768] / b00f [8] = conv0_0 of
+ * block i with LN_A = prompt_norms[i-1] folded in; fold [160] = LN_B (prompt_norms[i]) + conv0_1 of block i folded
+ * onto the previous block's s8 through its conv1x1 ([768][8]): c8 = rstd (Mc s + mc) + cb, rstd = 1 / sqrt(s'G s +
+ * 2 g.s + gb + 1e-6); layout Mc [8][8] at 0, mc at 64, cb at 72, G [8][8] at 80, g at 144, gb at 152.            */
+int mmt_prompt_fold(const float* conv0_0_w, const float* conv0_0_b, const float* ln_a_w, const float* ln_a_b,
+                    const float* conv0_1_w, const float* conv0_1_b, const float* ln_b_w, const float* ln_b_b,
+                    const float* conv1x1_prev_w, const float* conv1x1_prev_b, float* w00f, float* b00f, float* fold);
+/* tests / tuning: pin the slots per wave of the prompt kernels (1, 2, 4) and the rows per workgroup of the LayerNorm
+ * and final-norm launches (1, 4); -1 restores the heuristic (or MMT_TOK_R / MMT_ROW_FEW) */
+int mmt_tokens_force_config(int rows_per_wave, int rows_per_block);
 
 #ifdef __cplusplus
 }

@@ -380,6 +380,61 @@ void fold_conv(mmt_engine* e, const std::string& p, int cout, int cin, std::vect
   }
 }
 
+// The folded constants of deep prompt layer i (host only, formed in double, stored as fp32), from the raw tensors:
+//   w00f / b00f: conv0_0(LN_A(x)) = (W00 diag gA) xhat + (b00 + W00 bA), LN_A = prompt_norms[i-1]
+//   fold:        PromptFold (kernels.h) from LN_B = prompt_norms[i], conv0_1 of block i and conv1x1 of block i-1
+// W00, W01: [8][768]; V: [768][8]
+void prompt_fold(const float* W00, const float* b00, const float* gA, const float* bA, const float* W, const float* w0,
+                 const float* g, const float* bb, const float* V, const float* v0, float* wf, float* bf, float* f) {
+  for (int k = 0; k < 8; ++k) {
+    double acc = b00[k];
+    for (int c = 0; c < C; ++c) {
+      wf[(size_t)k * C + c] = (float)((double)W00[(size_t)k * C + c] * gA[c]);
+      acc += (double)W00[(size_t)k * C + c] * bA[c];
+    }
+    bf[k] = (float)acc;
+  }
+  double cm[8] = {0}, bm = 0;
+  for (int c = 0; c < C; ++c) {
+    for (int j = 0; j < 8; ++j) cm[j] += V[c * 8 + j];
+    bm += v0[c];
+  }
+  for (int j = 0; j < 8; ++j) cm[j] /= C;
+  bm /= C;
+  std::vector<double> Vc((size_t)C * 8), vc(C);
+  for (int c = 0; c < C; ++c) {
+    for (int j = 0; j < 8; ++j) Vc[c * 8 + j] = V[c * 8 + j] - cm[j];
+    vc[c] = v0[c] - bm;
+  }
+  for (int i = 0; i < FOLD_N; ++i) f[i] = 0.f;
+  for (int k = 0; k < 8; ++k) {
+    double mc = 0, cb = w0[k];
+    double Mk[8] = {0};
+    for (int c = 0; c < C; ++c) {
+      const double wg = (double)W[k * C + c] * g[c];
+      for (int j = 0; j < 8; ++j) Mk[j] += wg * Vc[c * 8 + j];
+      mc += wg * vc[c];
+      cb += (double)W[k * C + c] * bb[c];
+    }
+    for (int j = 0; j < 8; ++j) f[FOLD_MC + k * 8 + j] = (float)Mk[j];
+    f[FOLD_mc + k] = (float)mc;
+    f[FOLD_cb + k] = (float)cb;
+  }
+  double gb = 0;
+  for (int j = 0; j < 8; ++j) {
+    double gj = 0;
+    for (int l = 0; l < 8; ++l) {
+      double G = 0;
+      for (int c = 0; c < C; ++c) G += Vc[c * 8 + j] * Vc[c * 8 + l];
+      f[FOLD_G + j * 8 + l] = (float)(G / C);
+    }
+    for (int c = 0; c < C; ++c) gj += Vc[c * 8 + j] * vc[c];
+    f[FOLD_g + j] = (float)(gj / C);
+  }
+  for (int c = 0; c < C; ++c) gb += vc[c] * vc[c];
+  f[FOLD_gb] = (float)(gb / C);
+}
+
 int pack_weights(mmt_engine* e) {
   const auto& c = e->cfg;
   const bool vipt = c.model == MMT_MODEL_VIPT;
@@ -415,70 +470,18 @@ int pack_weights(mmt_engine* e) {
     TRY(upload_f32(e, &w.nb, H(e, "backbone.prompt_norms." + std::to_string(i) + ".bias")));
     w.fold = nullptr;
     w.w00f = w.b00f = nullptr;
-    if (i >= 1) {   // conv0_0(LN_A(x)) = (w00 diag gA) xhat + (b00 + w00 bA), in double
-      const auto& W = H(e, p + "conv0_0.weight");
-      const auto& b0 = H(e, p + "conv0_0.bias");
-      const auto& gA = H(e, "backbone.prompt_norms." + std::to_string(i - 1) + ".weight");
-      const auto& bA = H(e, "backbone.prompt_norms." + std::to_string(i - 1) + ".bias");
-      std::vector<float> wf((size_t)8 * C), bf(8);
-      for (int k = 0; k < 8; ++k) {
-        double acc = b0[k];
-        for (int c = 0; c < C; ++c) {
-          wf[(size_t)k * C + c] = (float)((double)W[(size_t)k * C + c] * gA[c]);
-          acc += (double)W[(size_t)k * C + c] * bA[c];
-        }
-        bf[k] = (float)acc;
-      }
+    if (i >= 1) {   // the deep layers' folded constants (prompt_fold)
+      const std::string pp = "backbone.prompt_blocks." + std::to_string(i - 1) + ".";
+      std::vector<float> wf((size_t)8 * C), bf(8), f(FOLD_N, 0.f);
+      prompt_fold(H(e, p + "conv0_0.weight").data(), H(e, p + "conv0_0.bias").data(),
+                  H(e, "backbone.prompt_norms." + std::to_string(i - 1) + ".weight").data(),
+                  H(e, "backbone.prompt_norms." + std::to_string(i - 1) + ".bias").data(),
+                  H(e, p + "conv0_1.weight").data(), H(e, p + "conv0_1.bias").data(),
+                  H(e, "backbone.prompt_norms." + std::to_string(i) + ".weight").data(),
+                  H(e, "backbone.prompt_norms." + std::to_string(i) + ".bias").data(),
+                  H(e, pp + "conv1x1.weight").data(), H(e, pp + "conv1x1.bias").data(), wf.data(), bf.data(), f.data());
       TRY(upload_f32(e, &w.w00f, wf));
       TRY(upload_f32(e, &w.b00f, bf));
-    }
-    if (i >= 1) {   // PromptFold, in double (kernels.h)
-      const auto& W = H(e, p + "conv0_1.weight");            // [8][768]
-      const auto& w0 = H(e, p + "conv0_1.bias");
-      const auto& g = H(e, "backbone.prompt_norms." + std::to_string(i) + ".weight");
-      const auto& bb = H(e, "backbone.prompt_norms." + std::to_string(i) + ".bias");
-      const std::string pp = "backbone.prompt_blocks." + std::to_string(i - 1) + ".";
-      const auto& V = H(e, pp + "conv1x1.weight");            // [768][8]
-      const auto& v0 = H(e, pp + "conv1x1.bias");
-      double cm[8] = {0}, bm = 0;
-      for (int c = 0; c < C; ++c) {
-        for (int j = 0; j < 8; ++j) cm[j] += V[c * 8 + j];
-        bm += v0[c];
-      }
-      for (int j = 0; j < 8; ++j) cm[j] /= C;
-      bm /= C;
-      std::vector<double> Vc((size_t)C * 8), vc(C);
-      for (int c = 0; c < C; ++c) {
-        for (int j = 0; j < 8; ++j) Vc[c * 8 + j] = V[c * 8 + j] - cm[j];
-        vc[c] = v0[c] - bm;
-      }
-      std::vector<float> f(FOLD_N, 0.f);
-      for (int k = 0; k < 8; ++k) {
-        double mc = 0, cb = w0[k];
-        double Mk[8] = {0};
-        for (int c = 0; c < C; ++c) {
-          const double wg = (double)W[k * C + c] * g[c];
-          for (int j = 0; j < 8; ++j) Mk[j] += wg * Vc[c * 8 + j];
-          mc += wg * vc[c];
-          cb += (double)W[k * C + c] * bb[c];
-        }
-        for (int j = 0; j < 8; ++j) f[FOLD_MC + k * 8 + j] = (float)Mk[j];
-        f[FOLD_mc + k] = (float)mc;
-        f[FOLD_cb + k] = (float)cb;
-      }
-      double gb = 0;
-      for (int j = 0; j < 8; ++j) {
-        double gj = 0;
-        for (int l = 0; l < 8; ++l) {
-          double G = 0;
-          for (int c = 0; c < C; ++c) G += Vc[c * 8 + j] * Vc[c * 8 + l];
-          f[FOLD_G + j * 8 + l] = (float)(G / C);
-        }
-        for (int c = 0; c < C; ++c) gj += Vc[c * 8 + j] * vc[c];
-        f[FOLD_g + j] = (float)(gj / C);
-      }
-      for (int c = 0; c < C; ++c) gb += vc[c] * vc[c];
-      f[FOLD_gb] = (float)(gb / C);
       TRY(upload_f32(e, &w.fold, f));
     }
   }
@@ -744,6 +747,12 @@ int run_gemm(mmt_engine* e, bool& ok, hipStream_t st, const char* cls, const Gem
   return ks;
 }
 
+// a token kernel's launcher declined (more than 1 024 search tokens / slots per sequence): nothing was launched
+void token_fail(mmt_engine* e, bool& ok, const char* what) {
+  e->err = std::string(what) + ": more than 1024 tokens per sequence";
+  ok = false;
+}
+
 // a residual-stream GEMM (EPI_RESID_F32 into X) whose split-K combine is left to the consuming row kernel
 RowReduce run_resid_gemm(mmt_engine* e, bool& ok, hipStream_t st, const char* cls, GemmArgs a) {
   a.defer_reduce = a.ws ? 1 : 0;
@@ -882,7 +891,8 @@ bool enqueue_forward(mmt_engine* e, int b0, int r0, int n, hipStream_t s, int pa
     pa.srcA_rows = L;
     pa.srcB = q_tok_aux;
     pa.slot2pos = nullptr;
-    prompt_reduce(pa, s);   // fovea, P and X = tok_rgb + P + pos are formed with block 0's LN1
+    // fovea, P and X = tok_rgb + P + pos are formed with block 0's LN1
+    if (!prompt_reduce(pa, s)) token_fail(e, ok, "prompt_reduce");
   }
 
   int* gin = q_gidx0;
@@ -929,8 +939,8 @@ bool enqueue_forward(mmt_engine* e, int b0, int r0, int n, hipStream_t s, int pa
       la.out = q_Hn;
       la.out_lo = q_Hn_l;
       la.out_scale = w.ln1_s;
-      if (ln_mode == 2) prompt_reduce(pa, s);
-      prompt_expand_ln(la, s);
+      if (ln_mode == 2 && !prompt_reduce(pa, s)) token_fail(e, ok, "prompt_reduce");
+      if (!prompt_expand_ln(la, s)) token_fail(e, ok, "prompt_expand_ln");
     } else {
       layernorm(X, w.n1w, w.n1b, q_Hn, q_Hn_l, w.ln1_s, nullptr, n * Na, Na, nullptr, Na, nullptr, s, pend);
       pend = RowReduce{};
@@ -1006,7 +1016,7 @@ bool enqueue_forward(mmt_engine* e, int b0, int r0, int n, hipStream_t s, int pa
                                                   : nullptr;
       ++ce_stage;
       if (!ce_layernorm(ce_a, X, w.n2w, w.n2b, q_Hn, q_Hn_l, w.ln2_s, Na, X2, s, pend)) {
-        ce_select(ce_a, s);
+        if (!ce_select(ce_a, s)) token_fail(e, ok, "ce_select");
         layernorm(X, w.n2w, w.n2b, q_Hn, q_Hn_l, w.ln2_s, nullptr, n * (Lz + keep), Lz + keep, q_gather, Na, X2, s,
                   pend);
       }
@@ -1945,6 +1955,191 @@ int mmt_op_layernorm(const float* x, const float* w, const float* b, void* out_b
   layernorm(x, w, b, (bf16_t*)out_bf16, nullptr, 1.0f, out_f32, rows, rows, nullptr, rows, nullptr,
             (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+// ---- token kernels (tokens.hip)
+namespace {
+// a RowReduce from the C struct (null: nothing pending); false: bad fields
+bool to_row_reduce(const mmt_row_reduce* r, RowReduce& rr) {
+  rr = RowReduce{};
+  if (!r || !r->ws) return true;
+  if (r->ks < 1 || r->ks > 8 || r->slab < 0 || !r->bias) return false;
+  rr = RowReduce{r->ws, r->ks, r->slab, r->inv, r->bias};
+  return true;
+}
+// an index list of an operator-level call, read back and checked against [lo, hi) (tests and composing hosts:
+// synchronous)
+int check_index_list(const int* dev, size_t n, int lo, int hi) {
+  std::vector<int> h(n);
+  if (hipMemcpy(h.data(), dev, n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return MMT_E_HIP;
+  for (int v : h)
+    if (v < lo || v >= hi) return MMT_E_ARG;
+  return MMT_OK;
+}
+}  // namespace
+
+int mmt_tokens_force_config(int rows_per_wave, int rows_per_block) {
+  return tokens_force_config(rows_per_wave, rows_per_block) ? MMT_OK : MMT_E_ARG;
+}
+
+int mmt_op_layernorm_ex(const float* x, const float* w, const float* b, void* out, void* out_lo, float out_scale,
+                        float* out_f32, int rows, int rows_per_seq, const int* gather, int in_rows_per_seq,
+                        float* xcopy, const mmt_row_reduce* reduce, void* stream) {
+  RowReduce rr;
+  if (!x || !w || !b || rows <= 0 || rows_per_seq <= 0 || rows % rows_per_seq || (!out && !out_f32 && !xcopy) ||
+      (out_lo && !out) || !to_row_reduce(reduce, rr))
+    return MMT_E_ARG;
+  if (gather) {
+    if (in_rows_per_seq <= 0) return MMT_E_ARG;
+    const int r = check_index_list(gather, (size_t)rows, 0, in_rows_per_seq);
+    if (r) return r;
+  }
+  layernorm(x, w, b, (bf16_t*)out, (bf16_t*)out_lo, out_scale, out_f32, rows, rows_per_seq, gather, in_rows_per_seq,
+            xcopy, (hipStream_t)stream, rr);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_ce_select(const mmt_ce_args* c, int fused, const float* x, const float* w, const float* b, void* out,
+                     void* out_lo, float out_scale, int in_rows_per_seq, float* xcopy, const mmt_row_reduce* reduce,
+                     void* stream) {
+  RowReduce rr;
+  if (!c || c->B < 1 || c->Lz < 0 || c->Ls < 1 || c->Ls > 1024 || c->keep < 1 || c->keep > c->Ls || c->heads < 1 ||
+      c->Lx < c->Ls || c->removed_off < 0 || c->removed_off + (c->Ls - c->keep) > c->Lx || !c->prob || !c->gidx_in ||
+      !c->gidx_out || !c->gather || !c->slot2pos || !c->removed)
+    return MMT_E_ARG;
+  if (fused < 0 || fused > 1 || !x || !w || !b || (!out && !xcopy) || (out_lo && !out) ||
+      in_rows_per_seq < c->Lz + c->Ls || !to_row_reduce(reduce, rr))
+    return MMT_E_ARG;
+  const int r = check_index_list(c->gidx_in, (size_t)c->B * c->Ls, 0, c->Lx);
+  if (r) return r;
+  CEArgs a{};
+  a.B = c->B;
+  a.Lz = c->Lz;
+  a.Ls = c->Ls;
+  a.keep = c->keep;
+  a.heads = c->heads;
+  a.Lx = c->Lx;
+  a.prob = c->prob;
+  a.gidx_in = c->gidx_in;
+  a.gidx_out = c->gidx_out;
+  a.gather = c->gather;
+  a.slot2pos = c->slot2pos;
+  a.removed = c->removed;
+  a.removed_off = c->removed_off;
+  const hipStream_t s = (hipStream_t)stream;
+  if (fused) {   // the one-launch form or nothing: a caller asking for it is not handed the two-launch result
+    if (!ce_layernorm(a, x, w, b, (bf16_t*)out, (bf16_t*)out_lo, out_scale, in_rows_per_seq, xcopy, s, rr))
+      return MMT_E_STATE;
+  } else {       // the engine's two-launch branch (enqueue_forward)
+    if (!ce_select(a, s)) return MMT_E_ARG;
+    layernorm(x, w, b, (bf16_t*)out, (bf16_t*)out_lo, out_scale, nullptr, c->B * (c->Lz + c->keep), c->Lz + c->keep,
+              c->gather, in_rows_per_seq, xcopy, s, rr);
+  }
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_final_norm_recover(const float* X, int rows_per_seq, const int* slot2pos, const float* w, const float* b,
+                              int B, int Lz, int Lx, void* feat, void* feat_lo, float feat_scale, float* feat_f32,
+                              const mmt_row_reduce* reduce, void* stream) {
+  RowReduce rr;
+  if (!X || !slot2pos || !w || !b || !feat || B < 1 || Lz < 0 || Lx < 1 || rows_per_seq < Lz || rows_per_seq < 1 ||
+      !to_row_reduce(reduce, rr))
+    return MMT_E_ARG;
+  const int r = check_index_list(slot2pos, (size_t)B * Lx, -1, rows_per_seq);
+  if (r) return r;
+  final_norm_recover(X, rows_per_seq, slot2pos, w, b, B, Lz, Lx, (bf16_t*)feat, (bf16_t*)feat_lo, feat_scale, feat_f32,
+                     (hipStream_t)stream, rr);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_prompt_reduce(const mmt_prompt_args* p, const mmt_row_reduce* reduce, void* stream) {
+  RowReduce rr;
+  if (!p || p->layer < 0 || p->B < 1 || p->Lz < 0 || p->Lx < 1 || p->Lz + p->Lx > 1024 || !p->srcA || !p->w00 ||
+      !p->b00 || !p->a8 || !p->c8 || !to_row_reduce(reduce, rr))
+    return MMT_E_ARG;
+  PromptArgs a{};
+  if (p->layer == 0) {
+    if (!p->srcB || !p->lnA_w || !p->lnA_b || !p->lnB_w || !p->lnB_b || !p->w01 || !p->b01 || rr.ws) return MMT_E_ARG;
+    a.srcA_rows = p->Lz + p->Lx;
+  } else {
+    if (!p->slot2pos || !p->fold || !p->a8p || !p->c8p || p->srcA_rows < p->Lz || p->srcA_rows < 1) return MMT_E_ARG;
+    const int r = check_index_list(p->slot2pos, (size_t)p->B * p->Lx, -1, p->srcA_rows);
+    if (r) return r;
+    a.srcA_rows = p->srcA_rows;
+  }
+  a.layer = p->layer;
+  a.B = p->B;
+  a.Lz = p->Lz;
+  a.Lx = p->Lx;
+  a.srcA = p->srcA;
+  a.srcB = p->srcB;
+  a.slot2pos = p->slot2pos;
+  a.lnA_w = p->lnA_w;
+  a.lnA_b = p->lnA_b;
+  a.lnB_w = p->lnB_w;
+  a.lnB_b = p->lnB_b;
+  a.w00 = p->w00;
+  a.b00 = p->b00;
+  a.w01 = p->w01;
+  a.b01 = p->b01;
+  a.fold = p->fold;
+  a.a8 = p->a8;
+  a.c8 = p->c8;
+  a.a8p = p->a8p;
+  a.c8p = p->c8p;
+  a.smooth_p = p->smooth_p;
+  a.fstat_p = p->fstat_p;
+  a.rr = rr;
+  if (!prompt_reduce(a, (hipStream_t)stream)) return MMT_E_ARG;
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_prompt_expand_ln(const mmt_ln_prompt_args* p, void* stream) {
+  if (!p || (p->mode != 1 && p->mode != 2) || p->rows < 1 || p->rows_per_seq < 1 || p->rows % p->rows_per_seq ||
+      p->Lz < 0 || p->Lx < 1 || p->Lz + p->Lx > 1024 || !p->X || !p->a8 || !p->c8 || !p->w1 || !p->b1 || !p->w || !p->b ||
+      !p->out)
+    return MMT_E_ARG;
+  if (p->mode == 1) {
+    if (!p->tok_rgb || !p->pos || p->rows_per_seq != p->Lz + p->Lx) return MMT_E_ARG;
+  } else {
+    if (!p->gidx || p->rows_per_seq <= p->Lz || p->rows_per_seq > p->Lz + p->Lx) return MMT_E_ARG;
+    const int r = check_index_list(p->gidx, (size_t)(p->rows / p->rows_per_seq) * (p->rows_per_seq - p->Lz), 0, p->Lx);
+    if (r) return r;
+  }
+  LnPromptArgs a{};
+  a.mode = p->mode;
+  a.rows = p->rows;
+  a.rows_per_seq = p->rows_per_seq;
+  a.Lz = p->Lz;
+  a.Lx = p->Lx;
+  a.X = p->X;
+  a.a8 = p->a8;
+  a.c8 = p->c8;
+  a.smooth = p->smooth;
+  a.fstat = p->fstat;
+  a.w1 = p->w1;
+  a.b1 = p->b1;
+  a.tok_rgb = p->tok_rgb;
+  a.pos = p->pos;
+  a.gidx = p->gidx;
+  a.w = p->w;
+  a.b = p->b;
+  a.out = (bf16_t*)p->out;
+  a.out_lo = (bf16_t*)p->out_lo;
+  a.out_scale = p->out_scale;
+  if (!prompt_expand_ln(a, (hipStream_t)stream)) return MMT_E_ARG;
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_prompt_fold(const float* conv0_0_w, const float* conv0_0_b, const float* ln_a_w, const float* ln_a_b,
+                    const float* conv0_1_w, const float* conv0_1_b, const float* ln_b_w, const float* ln_b_b,
+                    const float* conv1x1_prev_w, const float* conv1x1_prev_b, float* w00f, float* b00f, float* fold) {
+  if (!conv0_0_w || !conv0_0_b || !ln_a_w || !ln_a_b || !conv0_1_w || !conv0_1_b || !ln_b_w || !ln_b_b ||
+      !conv1x1_prev_w || !conv1x1_prev_b || !w00f || !b00f || !fold)
+    return MMT_E_ARG;
+  prompt_fold(conv0_0_w, conv0_0_b, ln_a_w, ln_a_b, conv0_1_w, conv0_1_b, ln_b_w, ln_b_b, conv1x1_prev_w,
+              conv1x1_prev_b, w00f, b00f, fold);
+  return MMT_OK;
 }
 
 }  // extern "C"

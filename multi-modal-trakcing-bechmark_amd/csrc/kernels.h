@@ -99,6 +99,9 @@ void ce_rows(const CeRowsArgs& a, hipStream_t s);
 void layernorm(const float* x, const float* w, const float* b, bf16_t* out_bf16, bf16_t* out_lo, float out_scale,
                float* out_f32, int rows, int rows_per_seq, const int* gather, int in_rows_per_seq, float* xcopy,
                hipStream_t s, const RowReduce& rr = RowReduce{});
+// tests / tuning: pin the slots per wave of the deep prompt and prompt + LN1 kernels (1, 2, 4) and the rows per
+// workgroup of layernorm / final_norm_recover (1, 4); -1: the heuristic (or MMT_TOK_R / MMT_ROW_FEW).  false: bad value
+bool tokens_force_config(int rows_per_wave, int rows_per_block);
 
 // ---------------------------------------------------------------- ViPT prompt blocks
 struct PromptArgs {
@@ -132,7 +135,8 @@ struct PromptArgs {
 //   Mc = (W diag g) V', mc = (W diag g) v0', cb = W b + w0, G = V'^T V' / 768, g = V'^T v0' / 768,
 //   gb = |v0'|^2 / 768   (LN_B(P_prev) -> conv0_1, vit_ce_prompt.py:292-300, without forming P_prev)
 enum { FOLD_MC = 0, FOLD_mc = 64, FOLD_cb = 72, FOLD_G = 80, FOLD_g = 144, FOLD_gb = 152, FOLD_N = 160 };
-void prompt_reduce(const PromptArgs& a, hipStream_t s);
+// false, nothing launched: a deep layer with Lz + Lx > 1024 (the fovea statistics stage a sequence's a8 in LDS)
+bool prompt_reduce(const PromptArgs& a, hipStream_t s);
 
 // LN1 of a block with the prompt residual fused in (writes the updated residual X and LN(X))
 struct LnPromptArgs {
@@ -152,7 +156,8 @@ struct LnPromptArgs {
 };
 // the fovea statistics of the row's sequence, s8 of its slot, the prompt residual (conv1x1 of s8, formed per
 // row from an LDS copy of conv1x1) and LN1, for the compact rows
-void prompt_expand_ln(const LnPromptArgs& a, hipStream_t s);
+// (false, nothing launched: Lz + Lx > 1024)
+bool prompt_expand_ln(const LnPromptArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- candidate elimination
 struct CEArgs {
@@ -170,7 +175,7 @@ struct CEArgs {
   float* keys_out;        // [B][Lx] the head-mean score of every surviving slot, by slot id
   int keys_pitch;         // floats between sequences of forced / keys_out
 };
-void ce_select(const CEArgs& a, hipStream_t s);
+bool ce_select(const CEArgs& a, hipStream_t s);   // false, nothing launched: Ls > 1024 (the keys live in LDS)
 // ce_select + the LN2 that gathers the survivors (layernorm with a.gather), one launch for few sequences; false:
 // not taken (the caller launches the two)
 bool ce_layernorm(const CEArgs& a, const float* x, const float* w, const float* b, bf16_t* out_bf16, bf16_t* out_lo,

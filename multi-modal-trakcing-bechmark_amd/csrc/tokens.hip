@@ -309,9 +309,24 @@ __global__ __launch_bounds__(256) void ln_kernel(const float* x, const float* w,
 // rows per workgroup: 4, or 1 for the few rows of one or two sequences -- each workgroup's row, split-K slabs and
 // affine then come into a CU of their own instead of four rows' worth into one (the launch is per-CU intake bound
 // there: a row with four fc2 slabs is 15 KB)
+// MMT_ROW_FEW / MMT_TOK_R (tuning): the row count up to which a workgroup takes one row, and the slots per wave of
+// the deep prompt / LN1 kernels (tok_rows_per_wave); tokens_force_config overrides either (tests), -1: not forced
+static const int g_env_row_few = getenv("MMT_ROW_FEW") ? atoi(getenv("MMT_ROW_FEW")) : 1024;
+static const int g_env_tok_r = getenv("MMT_TOK_R") ? atoi(getenv("MMT_TOK_R")) : 0;
+static int g_force_tok_r = -1, g_force_rpb = -1;
+
+bool tokens_force_config(int rows_per_wave, int rows_per_block) {
+  const bool okw = rows_per_wave == -1 || rows_per_wave == 1 || rows_per_wave == 2 || rows_per_wave == 4;
+  const bool okb = rows_per_block == -1 || rows_per_block == 1 || rows_per_block == 4;
+  if (!okw || !okb) return false;
+  g_force_tok_r = rows_per_wave;
+  g_force_rpb = rows_per_block;
+  return true;
+}
+
 static int rows_per_block(int rows) {
-  static const int few = getenv("MMT_ROW_FEW") ? atoi(getenv("MMT_ROW_FEW")) : 1024;
-  return rows <= few ? 1 : 4;
+  if (g_force_rpb > 0) return g_force_rpb;
+  return rows <= g_env_row_few ? 1 : 4;
 }
 
 void layernorm(const float* x, const float* w, const float* b, bf16_t* out_bf16, bf16_t* out_lo, float out_scale,
@@ -545,13 +560,14 @@ __global__ __launch_bounds__(TOK_THREADS) void prompt_reduce_deep_kernel(const P
 // slots per wave of the deep prompt / LN1 kernels: 2 from 8 sequences up (the weight fill and fovea statistics of a
 // block amortised over 16 rows), 1 below (a sequence's rows spread over more blocks); MMT_TOK_R (tuning) forces it
 static int tok_rows_per_wave(int B) {
-  static const int forced = getenv("MMT_TOK_R") ? atoi(getenv("MMT_TOK_R")) : 0;
+  const int forced = g_force_tok_r > 0 ? g_force_tok_r : g_env_tok_r;
   if (forced == 1 || forced == 2 || forced == 4) return forced;
   return B >= 8 ? 2 : 1;
 }
 
-void prompt_reduce(const PromptArgs& a, hipStream_t s) {
+bool prompt_reduce(const PromptArgs& a, hipStream_t s) {
   const int L = a.Lz + a.Lx;
+  if (a.layer != 0 && L > FOVEA_MAX_TOKENS) return false;   // the fovea staging holds 1 024 slots
   if (a.layer == 0) {
     const int waves = (a.B * L + PR_ROWS - 1) / PR_ROWS;
     hipLaunchKernelGGL(prompt_reduce_kernel, dim3((waves + 3) / 4), dim3(256), 0, s, a);
@@ -570,6 +586,7 @@ void prompt_reduce(const PromptArgs& a, hipStream_t s) {
     else
       hipLaunchKernelGGL((prompt_reduce_deep_kernel<false, 1>), grid, dim3(TOK_THREADS), va_bytes, s, a);
   }
+  return true;
 }
 
 // ------------------------------------------------------------------ LN1 with the prompt residual fused
@@ -699,7 +716,8 @@ __global__ __launch_bounds__(TOK_THREADS) __attribute__((amdgpu_waves_per_eu(LNP
   RSTAMP_RT(1, 5);
 }
 
-void prompt_expand_ln(const LnPromptArgs& a, hipStream_t s) {
+bool prompt_expand_ln(const LnPromptArgs& a, hipStream_t s) {
+  if (a.Lz + a.Lx > FOVEA_MAX_TOKENS) return false;   // the fovea staging holds 1 024 slots
   const int B = a.rows / a.rows_per_seq, R = a.mode == 1 ? std::min(tok_rows_per_wave(B), 2) : tok_rows_per_wave(B);
   const dim3 grid((a.rows_per_seq + TOK_ROWS * R - 1) / (TOK_ROWS * R), B);
   const size_t va_bytes = (size_t)(a.Lz + a.Lx) * 8 * sizeof(float);
@@ -713,6 +731,7 @@ void prompt_expand_ln(const LnPromptArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((ln_prompt_kernel<2, 2>), grid, dim3(TOK_THREADS), va_bytes, s, a);
   else
     hipLaunchKernelGGL((ln_prompt_kernel<2, 1>), grid, dim3(TOK_THREADS), va_bytes, s, a);
+  return true;
 }
 
 // ------------------------------------------------------------------ candidate elimination
@@ -776,8 +795,10 @@ __global__ __launch_bounds__(CE_THREADS) void ce_select_kernel(const CEArgs a) {
   for (int t = tid; t < a.Lz; t += CE_THREADS) a.gather[b * Ln + t] = t;
 }
 
-void ce_select(const CEArgs& a, hipStream_t s) {
+bool ce_select(const CEArgs& a, hipStream_t s) {
+  if (a.Ls > 1024) return false;   // key[1024] in LDS
   hipLaunchKernelGGL(ce_select_kernel, dim3(a.B), dim3(CE_THREADS), 0, s, a);
+  return true;
 }
 
 // Candidate elimination and the LN2 that gathers its survivors in one launch (few sequences: the one-sequence

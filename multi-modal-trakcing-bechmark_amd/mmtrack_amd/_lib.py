@@ -116,7 +116,38 @@ class MmtDimpResult(ctypes.Structure):
                 ("aux", ctypes.c_int * 4)]
 
 
-ABI_VERSION = 6   # include/mmtrack.h MMT_ABI_VERSION
+class MmtRowReduce(ctypes.Structure):
+    _fields_ = [("ws", ctypes.c_void_p), ("ks", ctypes.c_int), ("slab", ctypes.c_int64), ("inv", ctypes.c_float),
+                ("bias", ctypes.c_void_p)]
+
+
+class MmtCeArgs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("Lz", ctypes.c_int), ("Ls", ctypes.c_int), ("keep", ctypes.c_int),
+                ("heads", ctypes.c_int), ("Lx", ctypes.c_int), ("prob", ctypes.c_void_p), ("gidx_in", ctypes.c_void_p),
+                ("gidx_out", ctypes.c_void_p), ("gather", ctypes.c_void_p), ("slot2pos", ctypes.c_void_p),
+                ("removed", ctypes.c_void_p), ("removed_off", ctypes.c_int)]
+
+
+class MmtPromptArgs(ctypes.Structure):
+    _fields_ = [("layer", ctypes.c_int), ("B", ctypes.c_int), ("Lz", ctypes.c_int), ("Lx", ctypes.c_int),
+                ("srcA", ctypes.c_void_p), ("srcA_rows", ctypes.c_int), ("srcB", ctypes.c_void_p),
+                ("slot2pos", ctypes.c_void_p), ("lnA_w", ctypes.c_void_p), ("lnA_b", ctypes.c_void_p),
+                ("lnB_w", ctypes.c_void_p), ("lnB_b", ctypes.c_void_p), ("w00", ctypes.c_void_p),
+                ("b00", ctypes.c_void_p), ("w01", ctypes.c_void_p), ("b01", ctypes.c_void_p), ("fold", ctypes.c_void_p),
+                ("a8", ctypes.c_void_p), ("c8", ctypes.c_void_p), ("a8p", ctypes.c_void_p), ("c8p", ctypes.c_void_p),
+                ("smooth_p", ctypes.c_float), ("fstat_p", ctypes.c_void_p)]
+
+
+class MmtLnPromptArgs(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int), ("rows", ctypes.c_int), ("rows_per_seq", ctypes.c_int), ("Lz", ctypes.c_int),
+                ("Lx", ctypes.c_int), ("X", ctypes.c_void_p), ("a8", ctypes.c_void_p), ("c8", ctypes.c_void_p),
+                ("smooth", ctypes.c_float), ("fstat", ctypes.c_void_p), ("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p),
+                ("tok_rgb", ctypes.c_void_p), ("pos", ctypes.c_void_p), ("gidx", ctypes.c_void_p), ("w", ctypes.c_void_p),
+                ("b", ctypes.c_void_p), ("out", ctypes.c_void_p), ("out_lo", ctypes.c_void_p),
+                ("out_scale", ctypes.c_float)]
+
+
+ABI_VERSION = 7   # include/mmtrack.h MMT_ABI_VERSION
 
 # every symbol include/mmtrack.h declares: name -> (restype, argtypes)
 _P = ctypes.c_void_p
@@ -202,6 +233,15 @@ SIGNATURES = {
     "mmt_op_attention_f16x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _F, _P]),
     "mmt_op_ce_rows": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     "mmt_op_ce_rows_f16x3": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _F, _P]),
+    "mmt_op_layernorm_ex": (_I, [_P, _P, _P, _P, _P, _F, _P, _I, _I, _P, _I, _P, ctypes.POINTER(MmtRowReduce), _P]),
+    "mmt_op_ce_select": (_I, [ctypes.POINTER(MmtCeArgs), _I, _P, _P, _P, _P, _P, _F, _I, _P,
+                              ctypes.POINTER(MmtRowReduce), _P]),
+    "mmt_op_final_norm_recover": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _F, _P, ctypes.POINTER(MmtRowReduce),
+                                       _P]),
+    "mmt_op_prompt_reduce": (_I, [ctypes.POINTER(MmtPromptArgs), ctypes.POINTER(MmtRowReduce), _P]),
+    "mmt_op_prompt_expand_ln": (_I, [ctypes.POINTER(MmtLnPromptArgs), _P]),
+    "mmt_prompt_fold": (_I, [_P] * 13),
+    "mmt_tokens_force_config": (_I, [_I, _I]),
 }
 
 _lib = None
