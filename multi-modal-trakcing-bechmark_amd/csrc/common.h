@@ -17,7 +17,7 @@ __device__ __forceinline__ float bf2f(bf16_t x) {
 }
 
 // ---- fp32-faithful operands ("f16x3"): a value v, pre-multiplied by its tensor's power-of-two range
-// scale s (|v s| <= 2^14 by a host-computed bound, engine.cpp range_scale), travels as two fp16 halves
+// scale s (|v s| <= 2^14 by a host-computed bound, engine_weights.cpp range_scale), travels as two fp16 halves
 // hi = f16(v s), lo = f16(v s - hi) -- 22 significant bits -- and a product is hi*hi + lo*hi + hi*lo
 // (three fp16 MFMAs at the bf16 rate; the dropped lo*lo is 2^-22 relative).  The GEMM / attention
 // epilogues multiply the fp32 accumulator by 1 / (s_a s_w), exact for powers of two.

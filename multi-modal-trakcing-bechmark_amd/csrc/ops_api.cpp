@@ -1,0 +1,462 @@
+// C ABI of the stateless operator entry points (include/mmtrack.h: mmt_xcorr*, mmt_siamfc_*, mmt_op_*, the tuning
+// switches, mmt_prompt_fold): one kernel launcher each, no engine.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "engine.h"
+
+using namespace mmt;
+
+namespace {
+
+// a split-K workspace of the engine's size for the operator entry points (zeroed once); null: the GEMM runs unsplit
+float* op_workspace() {
+  static float* ws = nullptr;
+  if (!ws && hipMalloc(&ws, kSplitKWsElems * 4) == hipSuccess && hipMemset(ws, 0, kSplitKWsElems * 4) != hipSuccess) {
+    hipFree(ws);
+    ws = nullptr;
+  }
+  return ws;
+}
+
+// their zero page (GemmArgs::zero)
+const bf16_t* op_zero_page() {
+  static bf16_t* zero = nullptr;
+  if (!zero && hipMalloc(&zero, 256) == hipSuccess) hipMemset(zero, 0, 256);
+  return zero;
+}
+
+// the lists of an operator-level ce_rows call, read back and checked (tests and composing hosts: synchronous)
+int check_ce_rows(int B, int N, int heads, int lens_t, const int* rows, int pitch, const int* nrows, const float* prob) {
+  if (B <= 0 || N <= 0 || N > 1024 || heads <= 0 || lens_t <= 0 || lens_t >= N || !rows || !nrows || !prob || pitch <= 0)
+    return MMT_E_ARG;
+  std::vector<int> hn(B), hr((size_t)B * pitch);
+  if (hipMemcpy(hn.data(), nrows, (size_t)B * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(hr.data(), rows, hr.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return MMT_E_HIP;
+  for (int b = 0; b < B; ++b) {
+    if (hn[b] < 1 || hn[b] > lens_t || hn[b] > pitch) return MMT_E_ARG;
+    for (int i = 0; i < hn[b]; ++i) {
+      const int r = hr[(size_t)b * pitch + i];
+      if (r < 0 || r >= lens_t || (i > 0 && r <= hr[(size_t)b * pitch + i - 1])) return MMT_E_ARG;
+    }
+  }
+  return MMT_OK;
+}
+
+// a RowReduce from the C struct (null: nothing pending); false: bad fields
+bool to_row_reduce(const mmt_row_reduce* r, RowReduce& rr) {
+  rr = RowReduce{};
+  if (!r || !r->ws) return true;
+  if (r->ks < 1 || r->ks > 8 || r->slab < 0 || !r->bias) return false;
+  rr = RowReduce{r->ws, r->ks, r->slab, r->inv, r->bias};
+  return true;
+}
+// an index list of an operator-level call, read back and checked against [lo, hi) (tests and composing hosts:
+// synchronous)
+int check_index_list(const int* dev, size_t n, int lo, int hi) {
+  std::vector<int> h(n);
+  if (hipMemcpy(h.data(), dev, n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return MMT_E_HIP;
+  for (int v : h)
+    if (v < lo || v >= hi) return MMT_E_ARG;
+  return MMT_OK;
+}
+
+int siamfc_crop_impl(const uint8_t* frame, int Hh, int Ww, int Cc, int64_t row_stride, int n, const int* y0,
+                     const int* x0, const int* size, const int pad[3], int out_sz, float* out, int nhwc, void* stream) {
+  if (!frame || !out || !y0 || !x0 || !size || !pad || n <= 0 || n > 8 || Hh <= 0 || Ww <= 0 || Cc < 3 ||
+      row_stride < (int64_t)Ww * Cc || out_sz <= 0)
+    return MMT_E_ARG;
+  SiamCropArgs a{};
+  a.frame = frame;
+  a.stride = row_stride;
+  a.H = Hh;
+  a.W = Ww;
+  a.C = Cc;
+  a.n = n;
+  a.out_sz = out_sz;
+  for (int i = 0; i < n; ++i) {
+    if (size[i] < 1) return MMT_E_ARG;
+    a.y0[i] = y0[i];
+    a.x0[i] = x0[i];
+    a.size[i] = size[i];
+  }
+  for (int c = 0; c < 3; ++c) a.pad[c] = std::min(std::max(pad[c], 0), 255);
+  a.out = out;
+  a.nhwc = nhwc;
+  siamfc_crop(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmt_xcorr(const float* z, const float* x, float* out, int B, int Cc, int hz, int wz, int hx, int wx, float scale,
+              float bias, void* stream) {
+  if (!z || !x || !out || B <= 0 || Cc <= 0 || hz <= 0 || wz <= 0 || hx < hz || wx < wz || 16 * hz * wz > 16384)
+    return MMT_E_ARG;
+  xcorr(z, x, out, B, Cc, hz, wz, hx, wx, scale, bias, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_xcorr_nhwc(const float* z, int64_t z_batch_stride, const float* x, float* out, int B, int Cc, int hz, int wz,
+                   int hx, int wx, float scale, float bias, void* stream) {
+  if (!z || !x || !out || B <= 0 || Cc <= 0 || hz <= 0 || wz <= 0 || hx < hz || wx < wz || z_batch_stride < 0 ||
+      (int64_t)hz * wz * Cc > 16384 || ((Cc & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(z) |
+                                                           (uintptr_t)z_batch_stride * 4) & 15)))
+    return MMT_E_ARG;
+  xcorr_nhwc(z, z_batch_stride, x, out, B, Cc, hz, wz, hx, wx, scale, bias, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_siamfc_crop(const uint8_t* frame, int Hh, int Ww, int Cc, int64_t row_stride, int n, const int* y0,
+                    const int* x0, const int* size, const int pad[3], int out_sz, float* out, void* stream) {
+  return siamfc_crop_impl(frame, Hh, Ww, Cc, row_stride, n, y0, x0, size, pad, out_sz, out, 0, stream);
+}
+
+int mmt_siamfc_crop_nhwc(const uint8_t* frame, int Hh, int Ww, int Cc, int64_t row_stride, int n, const int* y0,
+                         const int* x0, const int* size, const int pad[3], int out_sz, float* out, void* stream) {
+  return siamfc_crop_impl(frame, Hh, Ww, Cc, row_stride, n, y0, x0, size, pad, out_sz, out, 1, stream);
+}
+
+int mmt_siamfc_response(const float* resp, int n, int r, int up, float scale_penalty, double window_influence,
+                        const double* hann1d, double hann_sum, float* scratch, float* result, void* stream) {
+  if (!resp || !hann1d || !scratch || !result || n <= 0 || n > 8 || r <= 1 || up < 2 || hann_sum <= 0)
+    return MMT_E_ARG;
+  SiamRespArgs a{};
+  a.resp = resp;
+  a.n = n;
+  a.r = r;
+  a.up = up;
+  a.penalty = scale_penalty;
+  a.one_minus_wi = (float)(1.0 - window_influence);
+  a.wi = window_influence;
+  a.hann_sum = hann_sum;
+  a.hann1d = hann1d;
+  a.scratch = scratch;
+  a.result = result;
+  siamfc_response(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_gemm(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* Cp, int64_t ldc,
+                const float* R, int64_t ldr, int M, int N, int K, int epi, int conv_hw, int conv_cin, int pos_rows,
+                void* stream) {
+  if (!A || !W || !Cp || M <= 0 || N <= 0 || K <= 0 || K % 64 || N % 32 || epi < 0 || epi > 6) return MMT_E_ARG;
+  if ((epi == EPI_RESID_F32 || epi == EPI_POS_F32) && !R) return MMT_E_ARG;
+  if (conv_hw > 0 && (conv_cin % 64 || K != 9 * conv_cin || (epi != EPI_RELU_BF16 && epi != EPI_RELU_F32)))
+    return MMT_E_ARG;
+  float* ws = op_workspace();
+  GemmArgs a{};
+  a.g[0] = GemmGroup{(const bf16_t*)A, nullptr, lda, (const bf16_t*)W, nullptr, ldw, bias, Cp, nullptr, ldc, R, ldr};
+  a.groups = 1;
+  a.zero = op_zero_page();
+  a.ws = ws;
+  a.ws_elems = ws ? kSplitKWsElems : 0;
+  a.M = M;
+  a.N = N;
+  a.K = K;
+  a.amode = conv_hw > 0 ? A_CONV3 : A_DENSE;
+  a.conv_hw = conv_hw;
+  a.conv_cin = conv_cin;
+  a.pos_rows = pos_rows > 0 ? pos_rows : 1;
+  if (gemm(a, epi, (hipStream_t)stream) < 0) return MMT_E_ARG;   // no kernel for this shape / epilogue: nothing ran
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_gemm_f16x3(const void* A_hi, const void* A_lo, int64_t lda, const void* W_hi, const void* W_lo, int64_t ldw,
+                      const float* bias, void* C, void* C_lo, int64_t ldc, const float* R, int64_t ldr, int M, int N, int K,
+                      int epi, float inv, float out_scale, int conv_hw, int conv_cin, void* stream) {
+  if (!A_hi || !A_lo || !W_hi || !W_lo || !C || M <= 0 || N <= 0 || K <= 0 || K % 64 || N % 32 || epi < 0 || epi > 6)
+    return MMT_E_ARG;
+  const bool out16 = epi == EPI_BF16 || epi == EPI_GELU_BF16 || epi == EPI_RELU_BF16;
+  if (out16 && !C_lo) return MMT_E_ARG;
+  if ((epi == EPI_RESID_F32 || epi == EPI_POS_F32) && !R) return MMT_E_ARG;
+  if (conv_hw > 0 && (conv_cin % 64 || K != 9 * conv_cin || (epi != EPI_RELU_BF16 && epi != EPI_RELU_F32)))
+    return MMT_E_ARG;
+  float* ws = op_workspace();
+  GemmArgs a{};
+  a.g[0] = GemmGroup{(const bf16_t*)A_hi, (const bf16_t*)A_lo, lda, (const bf16_t*)W_hi, (const bf16_t*)W_lo, ldw,
+                     bias, C, out16 ? C_lo : nullptr, ldc, R, ldr, inv, out_scale};
+  a.groups = 1;
+  a.split = 1;
+  a.ws = ws;
+  a.ws_elems = ws ? kSplitKWsElems : 0;
+  a.M = M;
+  a.N = N;
+  a.K = K;
+  a.amode = conv_hw > 0 ? A_CONV3 : A_DENSE;
+  a.conv_hw = conv_hw;
+  a.conv_cin = conv_cin;
+  a.pos_rows = 1;
+  if (gemm(a, epi, (hipStream_t)stream) < 0) return MMT_E_ARG;   // no kernel for this shape / epilogue: nothing ran
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_attention_f16x3(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, int B, int N, int heads,
+                           int ce_query, int ce_lens_t, float* ce_prob, float s_qkv, void* stream) {
+  if (!qkv_hi || !qkv_lo || !out_hi || !out_lo || B <= 0 || N <= 0 || N > 1024 || heads <= 0 || !(s_qkv > 0))
+    return MMT_E_ARG;
+  if (ce_query >= 0 && (!ce_prob || ce_lens_t < 0 || ce_lens_t >= N || ce_query >= N)) return MMT_E_ARG;
+  AttnArgs a{};
+  a.qkv = (const bf16_t*)qkv_hi;
+  a.qkv_lo = (const bf16_t*)qkv_lo;
+  a.out = (bf16_t*)out_hi;
+  a.out_lo = (bf16_t*)out_lo;
+  a.B = B;
+  a.N = N;
+  a.heads = heads;
+  a.ce_query = ce_query;
+  a.ce_lens_t = ce_lens_t;
+  a.ce_prob = ce_prob;
+  a.qk_inv = 0.125f / (s_qkv * s_qkv);   // the engine's arguments (engine_forward.cpp block), head dim 64
+  a.pv_inv = 1.0f / (16384.0f * s_qkv);
+  a.out_scale = s_qkv;
+  attention(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_ce_rows_f16x3(const void* qkv_hi, const void* qkv_lo, int B, int N, int heads, int lens_t, const int* rows,
+                         int rows_pitch, const int* nrows, float* ce_prob, float s_qkv, void* stream) {
+  if (!qkv_hi || !qkv_lo || !(s_qkv > 0)) return MMT_E_ARG;
+  const int r = check_ce_rows(B, N, heads, lens_t, rows, rows_pitch, nrows, ce_prob);
+  if (r) return r;
+  CeRowsArgs a{};
+  a.qkv = (const bf16_t*)qkv_hi;
+  a.qkv_lo = (const bf16_t*)qkv_lo;
+  a.B = B;
+  a.N = N;
+  a.heads = heads;
+  a.lens_t = lens_t;
+  a.rows = rows;
+  a.pitch = rows_pitch;
+  a.nrows = nrows;
+  a.prob = ce_prob;
+  a.qk_inv = 0.125f / (s_qkv * s_qkv);   // mmt_op_attention_f16x3's
+  ce_rows(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_ce_rows(const void* qkv, int B, int N, int heads, int lens_t, const int* rows, int rows_pitch,
+                   const int* nrows, float* ce_prob, void* stream) {
+  if (!qkv) return MMT_E_ARG;
+  const int r = check_ce_rows(B, N, heads, lens_t, rows, rows_pitch, nrows, ce_prob);
+  if (r) return r;
+  CeRowsArgs a{};
+  a.qkv = (const bf16_t*)qkv;
+  a.qkv_lo = nullptr;
+  a.B = B;
+  a.N = N;
+  a.heads = heads;
+  a.lens_t = lens_t;
+  a.rows = rows;
+  a.pitch = rows_pitch;
+  a.nrows = nrows;
+  a.prob = ce_prob;
+  ce_rows(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_gemm_stamps(void* dev_buf) { return gemm_set_stamps(dev_buf) == 0 ? MMT_OK : MMT_E_HIP; }
+
+int mmt_gemm_force_config(int cfg) {
+  gemm_force_config(cfg);
+  return MMT_OK;
+}
+
+int mmt_op_attention(const void* qkv, void* out, int B, int N, int heads, int ce_query, int ce_lens_t,
+                     float* ce_prob, void* stream) {
+  if (!qkv || !out || B <= 0 || N <= 0 || N > 1024 || heads <= 0) return MMT_E_ARG;
+  if (ce_query >= 0 && (!ce_prob || ce_lens_t < 0 || ce_lens_t >= N || ce_query >= N)) return MMT_E_ARG;
+  AttnArgs a{};
+  a.qkv = (const bf16_t*)qkv;
+  a.qkv_lo = nullptr;
+  a.out = (bf16_t*)out;
+  a.out_lo = nullptr;
+  a.B = B;
+  a.N = N;
+  a.heads = heads;
+  a.ce_query = ce_query;
+  a.ce_lens_t = ce_lens_t;
+  a.ce_prob = ce_prob;
+  attention(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_layernorm(const float* x, const float* w, const float* b, void* out_bf16, float* out_f32, int rows,
+                     void* stream) {
+  if (!x || !w || !b || rows <= 0 || (!out_bf16 && !out_f32)) return MMT_E_ARG;
+  layernorm(x, w, b, (bf16_t*)out_bf16, nullptr, 1.0f, out_f32, rows, rows, nullptr, rows, nullptr,
+            (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+// ---- token kernels (tokens.hip)
+int mmt_tokens_force_config(int rows_per_wave, int rows_per_block) {
+  return tokens_force_config(rows_per_wave, rows_per_block) ? MMT_OK : MMT_E_ARG;
+}
+
+int mmt_op_layernorm_ex(const float* x, const float* w, const float* b, void* out, void* out_lo, float out_scale,
+                        float* out_f32, int rows, int rows_per_seq, const int* gather, int in_rows_per_seq,
+                        float* xcopy, const mmt_row_reduce* reduce, void* stream) {
+  RowReduce rr;
+  if (!x || !w || !b || rows <= 0 || rows_per_seq <= 0 || rows % rows_per_seq || (!out && !out_f32 && !xcopy) ||
+      (out_lo && !out) || !to_row_reduce(reduce, rr))
+    return MMT_E_ARG;
+  if (gather) {
+    if (in_rows_per_seq <= 0) return MMT_E_ARG;
+    const int r = check_index_list(gather, (size_t)rows, 0, in_rows_per_seq);
+    if (r) return r;
+  }
+  layernorm(x, w, b, (bf16_t*)out, (bf16_t*)out_lo, out_scale, out_f32, rows, rows_per_seq, gather, in_rows_per_seq,
+            xcopy, (hipStream_t)stream, rr);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_ce_select(const mmt_ce_args* c, int fused, const float* x, const float* w, const float* b, void* out,
+                     void* out_lo, float out_scale, int in_rows_per_seq, float* xcopy, const mmt_row_reduce* reduce,
+                     void* stream) {
+  RowReduce rr;
+  if (!c || c->B < 1 || c->Lz < 0 || c->Ls < 1 || c->Ls > 1024 || c->keep < 1 || c->keep > c->Ls || c->heads < 1 ||
+      c->Lx < c->Ls || c->removed_off < 0 || c->removed_off + (c->Ls - c->keep) > c->Lx || !c->prob || !c->gidx_in ||
+      !c->gidx_out || !c->gather || !c->slot2pos || !c->removed)
+    return MMT_E_ARG;
+  if (fused < 0 || fused > 1 || !x || !w || !b || (!out && !xcopy) || (out_lo && !out) ||
+      in_rows_per_seq < c->Lz + c->Ls || !to_row_reduce(reduce, rr))
+    return MMT_E_ARG;
+  const int r = check_index_list(c->gidx_in, (size_t)c->B * c->Ls, 0, c->Lx);
+  if (r) return r;
+  CEArgs a{};
+  a.B = c->B;
+  a.Lz = c->Lz;
+  a.Ls = c->Ls;
+  a.keep = c->keep;
+  a.heads = c->heads;
+  a.Lx = c->Lx;
+  a.prob = c->prob;
+  a.gidx_in = c->gidx_in;
+  a.gidx_out = c->gidx_out;
+  a.gather = c->gather;
+  a.slot2pos = c->slot2pos;
+  a.removed = c->removed;
+  a.removed_off = c->removed_off;
+  const hipStream_t s = (hipStream_t)stream;
+  if (fused) {   // the one-launch form or nothing: a caller asking for it is not handed the two-launch result
+    if (!ce_layernorm(a, x, w, b, (bf16_t*)out, (bf16_t*)out_lo, out_scale, in_rows_per_seq, xcopy, s, rr))
+      return MMT_E_STATE;
+  } else {       // the engine's two-launch branch (engine_forward.cpp block)
+    if (!ce_select(a, s)) return MMT_E_ARG;
+    layernorm(x, w, b, (bf16_t*)out, (bf16_t*)out_lo, out_scale, nullptr, c->B * (c->Lz + c->keep), c->Lz + c->keep,
+              c->gather, in_rows_per_seq, xcopy, s, rr);
+  }
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_final_norm_recover(const float* X, int rows_per_seq, const int* slot2pos, const float* w, const float* b,
+                              int B, int Lz, int Lx, void* feat, void* feat_lo, float feat_scale, float* feat_f32,
+                              const mmt_row_reduce* reduce, void* stream) {
+  RowReduce rr;
+  if (!X || !slot2pos || !w || !b || !feat || B < 1 || Lz < 0 || Lx < 1 || rows_per_seq < Lz || rows_per_seq < 1 ||
+      !to_row_reduce(reduce, rr))
+    return MMT_E_ARG;
+  const int r = check_index_list(slot2pos, (size_t)B * Lx, -1, rows_per_seq);
+  if (r) return r;
+  final_norm_recover(X, rows_per_seq, slot2pos, w, b, B, Lz, Lx, (bf16_t*)feat, (bf16_t*)feat_lo, feat_scale, feat_f32,
+                     (hipStream_t)stream, rr);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_prompt_reduce(const mmt_prompt_args* p, const mmt_row_reduce* reduce, void* stream) {
+  RowReduce rr;
+  if (!p || p->layer < 0 || p->B < 1 || p->Lz < 0 || p->Lx < 1 || p->Lz + p->Lx > 1024 || !p->srcA || !p->w00 ||
+      !p->b00 || !p->a8 || !p->c8 || !to_row_reduce(reduce, rr))
+    return MMT_E_ARG;
+  PromptArgs a{};
+  if (p->layer == 0) {
+    if (!p->srcB || !p->lnA_w || !p->lnA_b || !p->lnB_w || !p->lnB_b || !p->w01 || !p->b01 || rr.ws) return MMT_E_ARG;
+    a.srcA_rows = p->Lz + p->Lx;
+  } else {
+    if (!p->slot2pos || !p->fold || !p->a8p || !p->c8p || p->srcA_rows < p->Lz || p->srcA_rows < 1) return MMT_E_ARG;
+    const int r = check_index_list(p->slot2pos, (size_t)p->B * p->Lx, -1, p->srcA_rows);
+    if (r) return r;
+    a.srcA_rows = p->srcA_rows;
+  }
+  a.layer = p->layer;
+  a.B = p->B;
+  a.Lz = p->Lz;
+  a.Lx = p->Lx;
+  a.srcA = p->srcA;
+  a.srcB = p->srcB;
+  a.slot2pos = p->slot2pos;
+  a.lnA_w = p->lnA_w;
+  a.lnA_b = p->lnA_b;
+  a.lnB_w = p->lnB_w;
+  a.lnB_b = p->lnB_b;
+  a.w00 = p->w00;
+  a.b00 = p->b00;
+  a.w01 = p->w01;
+  a.b01 = p->b01;
+  a.fold = p->fold;
+  a.a8 = p->a8;
+  a.c8 = p->c8;
+  a.a8p = p->a8p;
+  a.c8p = p->c8p;
+  a.smooth_p = p->smooth_p;
+  a.fstat_p = p->fstat_p;
+  a.rr = rr;
+  if (!prompt_reduce(a, (hipStream_t)stream)) return MMT_E_ARG;
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_prompt_expand_ln(const mmt_ln_prompt_args* p, void* stream) {
+  if (!p || (p->mode != 1 && p->mode != 2) || p->rows < 1 || p->rows_per_seq < 1 || p->rows % p->rows_per_seq ||
+      p->Lz < 0 || p->Lx < 1 || p->Lz + p->Lx > 1024 || !p->X || !p->a8 || !p->c8 || !p->w1 || !p->b1 || !p->w || !p->b ||
+      !p->out)
+    return MMT_E_ARG;
+  if (p->mode == 1) {
+    if (!p->tok_rgb || !p->pos || p->rows_per_seq != p->Lz + p->Lx) return MMT_E_ARG;
+  } else {
+    if (!p->gidx || p->rows_per_seq <= p->Lz || p->rows_per_seq > p->Lz + p->Lx) return MMT_E_ARG;
+    const int r = check_index_list(p->gidx, (size_t)(p->rows / p->rows_per_seq) * (p->rows_per_seq - p->Lz), 0, p->Lx);
+    if (r) return r;
+  }
+  LnPromptArgs a{};
+  a.mode = p->mode;
+  a.rows = p->rows;
+  a.rows_per_seq = p->rows_per_seq;
+  a.Lz = p->Lz;
+  a.Lx = p->Lx;
+  a.X = p->X;
+  a.a8 = p->a8;
+  a.c8 = p->c8;
+  a.smooth = p->smooth;
+  a.fstat = p->fstat;
+  a.w1 = p->w1;
+  a.b1 = p->b1;
+  a.tok_rgb = p->tok_rgb;
+  a.pos = p->pos;
+  a.gidx = p->gidx;
+  a.w = p->w;
+  a.b = p->b;
+  a.out = (bf16_t*)p->out;
+  a.out_lo = (bf16_t*)p->out_lo;
+  a.out_scale = p->out_scale;
+  if (!prompt_expand_ln(a, (hipStream_t)stream)) return MMT_E_ARG;
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_prompt_fold(const float* conv0_0_w, const float* conv0_0_b, const float* ln_a_w, const float* ln_a_b,
+                    const float* conv0_1_w, const float* conv0_1_b, const float* ln_b_w, const float* ln_b_b,
+                    const float* conv1x1_prev_w, const float* conv1x1_prev_b, float* w00f, float* b00f, float* fold) {
+  if (!conv0_0_w || !conv0_0_b || !ln_a_w || !ln_a_b || !conv0_1_w || !conv0_1_b || !ln_b_w || !ln_b_b ||
+      !conv1x1_prev_w || !conv1x1_prev_b || !w00f || !b00f || !fold)
+    return MMT_E_ARG;
+  prompt_fold(conv0_0_w, conv0_0_b, ln_a_w, ln_a_b, conv0_1_w, conv0_1_b, ln_b_w, ln_b_b, conv1x1_prev_w,
+              conv1x1_prev_b, w00f, b00f, fold);
+  return MMT_OK;
+}
+
+}  // extern "C"

@@ -47,7 +47,7 @@ def _p(t):
 
 
 def range_scale(m):
-    """engine.cpp range_scale: the power of two s with m * s <= 2^14 (m > 0)."""
+    """engine_weights.cpp range_scale: the power of two s with m * s <= 2^14 (m > 0)."""
     return 2.0 ** (14 - math.ceil(math.log2(m))) if m > 0 else 1.0
 
 

@@ -1,7 +1,7 @@
 """The benchmarked launch itself against the reference's golden outputs (GPU only).
 
 bench.py's headline line runs 32 sequences per mmt_track_batch launch with the launch sequence captured in a
-hipGraph and split into two stream halves of 16 sequences (engine.cpp enqueue_split), which selects a
+hipGraph and split into two stream halves of 16 sequences (engine_forward.cpp enqueue_split), which selects a
 different kernel set from the one-sequence launches of test_gpu_parity.py (the tables of test_gemm_plan.py, by
 layer width): qkv / fc1 on gemm256s_kernel, its 320 x 256 variant at 244 / 190 tokens and the 128 x 128 f16x3
 gemm_kernel (32-deep K-tiles) in the narrowest layers; proj / fc2 on gemm128w_kernel at 320 tokens, 128 x 192

@@ -33,7 +33,7 @@ def _stream():
 
 
 def range_scale(t):
-    """engine.cpp range_scale: the power of two s with max|t| * s <= 2^14."""
+    """engine_weights.cpp range_scale: the power of two s with max|t| * s <= 2^14."""
     m = float(t.abs().max())
     return 2.0 ** (14 - math.ceil(math.log2(m))) if m > 0 else 1.0
 

@@ -364,7 +364,7 @@ def test_pipelined_frames_equal_blocking(use_graphs):
 
 @pytest.mark.parametrize("nparts", ["2", "4"])
 def test_split_launch_equals_single(nparts, monkeypatch):
-    """A launch of >= 32 sequences runs as parts on separate HIP streams (engine.cpp enqueue_split, captured
+    """A launch of >= 32 sequences runs as parts on separate HIP streams (engine_forward.cpp enqueue_split, captured
     into one graph); every sequence's boxes equal that sequence tracked alone (to fp32 rounding: the parts'
     few-tile GEMMs may split K differently from a one-sequence launch)."""
     monkeypatch.setenv("MMT_NPARTS", nparts)
@@ -386,6 +386,41 @@ def test_split_launch_equals_single(nparts, monkeypatch):
             box, _ = single.track(0, fr[t])
             np.testing.assert_allclose(outs[t - 1][i], box, rtol=1e-5, atol=1e-3)
     single.close()
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_split_launch_buffer_views(engines, precision, monkeypatch):
+    """A launch whose parts see the activation buffers at a slot b0 != launch row r0 > 0: slots 1..3 of a four-slot
+    engine tracked as parts (b0=1, r0=0, n=1) and (b0=2, r0=1, n=2), once eagerly and once as a captured graph, with
+    and without the low halves, debug buffers on.  Per sequence: the crop byte for byte, the removed set, boxes
+    (test_batch_equals_single's tolerances) and scores (1e-3) of that sequence tracked alone."""
+    monkeypatch.setenv("MMT_OVERLAP_MIN", "2")
+    monkeypatch.setenv("MMT_NPARTS", "2")
+    eng = Engine(EngineConfig(max_batch=4, debug_outputs=True, use_graphs=True, precision=precision),
+                 synth.make_state_dict(0, **SHAPES["deep_rgbt"]))
+    single = engines("deep_rgbt", precision)
+    seqs = [synth.make_frames(60 + k, 3, 360, 480, 6, box=(180.0 + 15 * k, 140.0 + 5 * k, 38.0 + 6 * k, 30.0))
+            for k in range(3)]
+    for k, (fr, gt) in enumerate(seqs):
+        eng.initialize(k + 1, fr[0], list(gt[0]))
+    outs, crops, removed = [], None, None
+    for t in (1, 2):
+        outs.append(eng.track_batch(1, [seqs[k][0][t] for k in range(3)]))
+        if t == 1:
+            crops = [eng.debug("crop", k) for k in range(3)]
+            removed = [np.sort(eng.debug("removed", k)) for k in range(3)]
+    eng.close()
+    rtol, atol = (1e-6, 1e-4) if precision == "bf16" else (1e-5, 1e-3)
+    for k, (fr, gt) in enumerate(seqs):
+        single.initialize(0, fr[0], list(gt[0]))
+        for t in (1, 2):
+            box, score = single.track(0, fr[t])
+            if t == 1:
+                np.testing.assert_array_equal(crops[k], single.debug("crop"), err_msg=f"crop of sequence {k}")
+                np.testing.assert_array_equal(removed[k], np.sort(single.debug("removed")),
+                                              err_msg=f"removed set of sequence {k}")
+            np.testing.assert_allclose(outs[t - 1][0][k], box, rtol=rtol, atol=atol, err_msg=f"sequence {k} frame {t}")
+            assert abs(float(outs[t - 1][1][k]) - float(score)) <= 1e-3, (k, t)
 
 
 def test_ostrack384_tracker_sequence_matches_reference():
