@@ -90,8 +90,10 @@ const char* mmt_version(void);
  * instead of silently reading sample 0 everywhere).  6: candidate elimination over any template mask
  * (MMT_CE_TEMPLATE_MASK, mmt_set_ce_template_mask, mmt_op_ce_rows / _f16x3, timing class "ce_rows").  7: operator entry points of the token kernels
  * (mmt_op_layernorm_ex, mmt_op_ce_select, mmt_op_final_norm_recover, mmt_op_prompt_reduce,
- * mmt_op_prompt_expand_ln), mmt_prompt_fold and mmt_tokens_force_config. */
-#define MMT_ABI_VERSION 7
+ * mmt_op_prompt_expand_ln), mmt_prompt_fold and mmt_tokens_force_config.  8: operator entry points of the frame-side
+ * kernels (mmt_op_crop_patchify, mmt_op_crop_geometry, mmt_op_decode), mmt_crop_geometry_host and
+ * mmt_op_struct_layout. */
+#define MMT_ABI_VERSION 8
 int mmt_abi_version(void);
 /* pinned host memory that kernels read and write in place (mapped + coherent: a kernel sees the host's latest
  * writes and the host sees the kernel's after an event, with no copy launch) -- the DiMP pool's frame descriptors
@@ -563,6 +565,105 @@ int mmt_prompt_fold(const float* conv0_0_w, const float* conv0_0_b, const float*
 /* tests / tuning: pin the slots per wave of the prompt kernels (1, 2, 4) and the rows per workgroup of the LayerNorm
  * and final-norm launches (1, 4); -1 restores the heuristic (or MMT_TOK_R / MMT_ROW_FEW) */
 int mmt_tokens_force_config(int rows_per_wave, int rows_per_block);
+
+/* ---- frame-side kernels (csrc/imaging.hip): the first and the last kernel of a ViPT / OSTrack frame.  Every entry
+ *      checks its arguments first and returns MMT_E_ARG with nothing launched; the per-sequence frame descriptors and
+ *      the ring counters are read back and range-checked, so these calls are synchronous.  Arrays of the structs
+ *      below are device (or device-visible pinned) memory.                                                        */
+typedef struct mmt_crop_param {    /* one per sequence */
+  const uint8_t* frame;            /* H x W x C uint8, device; row stride in bytes */
+  int64_t stride;
+  int H, W, C;
+  int x1, y1, crop_sz;             /* the square crop (processing_utils.py:32-41) */
+  int pad_;
+} mmt_crop_param;
+typedef struct mmt_seq_state {     /* one per sequence: the tracker state kept on the device */
+  double box[4];                   /* self.state x, y, w, h */
+  double rf;                       /* resize_factor of the frame being tracked */
+  int err;                         /* MMT_E_BOX / MMT_E_ARG of this frame's geometry, else 0 */
+  int pad_;
+} mmt_seq_state;
+typedef struct mmt_track_out {     /* one per sequence of a launch */
+  double box[4];                   /* 'target_bbox' after the frame (the unchanged state on error) */
+  float score;                     /* 'best_score' */
+  int err;
+  int pad_[2];
+} mmt_track_out;
+typedef struct mmt_ring_args {     /* the host hand-off ring: kring entries of pitch records */
+  const mmt_crop_param* params;    /* [kring][pitch]: the frame fields of each launch's sequences */
+  mmt_track_out* outs;             /* [kring][pitch] */
+  int* ctr;                        /* the next launch's entry, in [0, kring) */
+  int* cur;                        /* the entry of the launch in flight */
+  int kring, pitch;
+} mmt_ring_args;
+/* the host's copy of the crop geometry (no GPU): crop_sz = ceil(sqrt(w h) factor), x1 = round-half-even(x + w/2 -
+ * crop_sz/2), rf = out_sz / crop_sz.  MMT_E_BOX (crop_sz < 1 or NaN) / MMT_E_ARG (crop_sz > 1e6, null pointers):
+ * the outputs are then the harmless crop 0, 0, 1 and rf = 1, as the kernels leave them.                       */
+int mmt_crop_geometry_host(const double box_xywh[4], double factor, int out_sz, int* x1, int* y1, int* crop_sz,
+                           double* rf);
+/* geometry_kernel: params[i].x1 / y1 / crop_sz, state[i].rf / err from state[i].box for i < n (one launch of one
+ * workgroup).  ring (or NULL): the frame fields of params[i] first come from ring->params[*ctr * pitch + i], then
+ * *cur = *ctr and *ctr advances mod kring.  gidx / slot2pos (both or neither) [n][Lx]: gidx[i][j] = j, slot2pos[i][j] =
+ * Lz + j.                                                                                                        */
+int mmt_op_crop_geometry(mmt_crop_param* params, mmt_seq_state* state, int n, double factor, int out_sz,
+                         const mmt_ring_args* ring, int* gidx, int* slot2pos, int Lz, int Lx, void* hip_stream);
+/* crop_kernel: sample_target + the cv2 resize + normalisation + the 16 x 16 patch unfold of B sequences.  Patch p
+ * (row-major over the (out_sz / 16)^2 grid) of sequence b is row b * rows_per_seq + row0 + p of A_rgb (channels 0..2)
+ * and A_aux (channels 3..5, C == 6), 768 values each at (c % 3) * 256 + ky * 16 + kx: bf16, or with the _lo buffers
+ * the fp16 hi / lo halves of the value * 4096.  dbg_patch (or NULL): the uint8 crop [B][out_sz][out_sz][C].       */
+typedef struct mmt_crop_args {
+  const mmt_crop_param* params;    /* [B] */
+  int B, out_sz, C;
+  void* A_rgb;
+  void* A_aux;
+  void* A_rgb_lo;
+  void* A_aux_lo;
+  int rows_per_seq, row0;
+  uint8_t* dbg_patch;
+} mmt_crop_args;
+/* the geometry formed inside the crop launch (crop_kernel<true>): params[b].x1 / y1 / crop_sz, state[b].rf / err and
+ * the index arrays as mmt_op_crop_geometry writes them; with use_ring the frame fields come from the ring entry *ctr
+ * and *cur is set, but *ctr is left to the decode launch (mmt_decode_args.ring_ctr)                              */
+typedef struct mmt_geom_args {
+  mmt_seq_state* state;            /* [B] */
+  double factor;
+  mmt_ring_args ring;
+  int use_ring;
+  int* gidx;
+  int* slot2pos;
+  int Lz, Lx;
+} mmt_geom_args;
+int mmt_op_crop_patchify(const mmt_crop_args* a, const mmt_geom_args* geom, void* hip_stream);
+/* decode_kernel: conv5 (1 x 1 over the 32 conv4 channels) + sigmoid / clamp, the Hann window, the first-occurrence
+ * argmax and the box gather; res [B][8] = cx, cy, w, h (normalised), score, index, 0, 0; maps (or NULL) [B][5][fs*fs]
+ * = ctr, size w, size h, offset x, offset y.  state (or NULL: result rows only) [B]: the box mapped back and clipped
+ * (vipt.py:84-88, box_ops.py:97-106, margin 10) into state[b].box and out[b]; a sequence with state[b].err set keeps
+ * its state.  ring_outs (or NULL): out[b] also goes to ring_outs[*ring_cur * ring_pitch + row0 + b]; ring_ctr (or
+ * NULL): *ring_ctr = (*ring_cur + 1) mod ring_kring.                                                            */
+typedef struct mmt_decode_args {
+  int B, fs;
+  const float* h4;                 /* [3][B][fs*fs][32]: the ctr, offset and size branches */
+  const float* w5;                 /* [5][32]: ctr, off_x, off_y, size_w, size_h */
+  const float* b5;                 /* [5] */
+  const float* hann;               /* [fs*fs] */
+  float* res;
+  float* maps;
+  mmt_seq_state* state;
+  const mmt_crop_param* params;    /* [B]: H and W of the frame */
+  mmt_track_out* out;              /* [B] */
+  int search_size;
+  mmt_track_out* ring_outs;
+  const int* ring_cur;
+  int ring_pitch, row0;
+  int* ring_ctr;
+  int ring_kring;
+} mmt_decode_args;
+int mmt_op_decode(const mmt_decode_args* a, void* hip_stream);
+/* the layout of a struct above as this library was compiled (a binding checks its mirror): out[0] = sizeof, then the
+ * offset of every field in declaration order; returns the number of values (0: unknown struct), writes at most cap.
+ * which: 0 mmt_crop_param, 1 mmt_seq_state, 2 mmt_track_out, 3 mmt_ring_args, 4 mmt_crop_args, 5 mmt_geom_args,
+ * 6 mmt_decode_args                                                                                              */
+int mmt_op_struct_layout(int which, size_t* out, int cap);
 
 #ifdef __cplusplus
 }

@@ -63,14 +63,9 @@ int alloc_acts(mmt_engine* e) {
 // crop geometry of processing_utils.py:32-41 in doubles with Python rounding (round half to even)
 int geometry(mmt_engine* e, const double box[4], double factor, int out_sz, int* x1, int* y1, int* crop_sz,
              double* rf) {
-  const double x = box[0], y = box[1], w = box[2], h = box[3];
-  const double cs = std::ceil(std::sqrt(w * h) * factor);
-  if (!(cs >= 1.0)) return e->fail(MMT_E_BOX, "Too small bounding box.");
-  if (cs > 1e6) return e->fail(MMT_E_ARG, "crop size out of range");
-  *crop_sz = (int)cs;
-  *x1 = (int)std::nearbyint(x + 0.5 * w - cs * 0.5);
-  *y1 = (int)std::nearbyint(y + 0.5 * h - cs * 0.5);
-  *rf = (double)out_sz / cs;
+  const int rc = mmt_crop_geometry_host(box, factor, out_sz, x1, y1, crop_sz, rf);   // the host's one copy
+  if (rc == MMT_E_BOX) return e->fail(MMT_E_BOX, "Too small bounding box.");
+  if (rc) return e->fail(MMT_E_ARG, "crop size out of range");
   return MMT_OK;
 }
 

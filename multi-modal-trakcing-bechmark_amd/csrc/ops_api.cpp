@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstddef>
 #include <vector>
 
 #include "engine.h"
@@ -90,9 +92,230 @@ int siamfc_crop_impl(const uint8_t* frame, int Hh, int Ww, int Cc, int64_t row_s
   return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
 }
 
+// ---- frame-side kernels: the C structs of include/mmtrack.h are the kernels' own (kernels.h), field for field
+#define SAME_FIELD(CT, KT, f) \
+  static_assert(offsetof(CT, f) == offsetof(KT, f) && sizeof(CT::f) == sizeof(KT::f), #CT "." #f)
+static_assert(sizeof(mmt_crop_param) == sizeof(CropParam), "mmt_crop_param");
+SAME_FIELD(mmt_crop_param, CropParam, frame);
+SAME_FIELD(mmt_crop_param, CropParam, stride);
+SAME_FIELD(mmt_crop_param, CropParam, H);
+SAME_FIELD(mmt_crop_param, CropParam, W);
+SAME_FIELD(mmt_crop_param, CropParam, C);
+SAME_FIELD(mmt_crop_param, CropParam, x1);
+SAME_FIELD(mmt_crop_param, CropParam, y1);
+SAME_FIELD(mmt_crop_param, CropParam, crop_sz);
+static_assert(sizeof(mmt_seq_state) == sizeof(SeqState), "mmt_seq_state");
+SAME_FIELD(mmt_seq_state, SeqState, box);
+SAME_FIELD(mmt_seq_state, SeqState, rf);
+SAME_FIELD(mmt_seq_state, SeqState, err);
+static_assert(sizeof(mmt_track_out) == sizeof(TrackOut), "mmt_track_out");
+SAME_FIELD(mmt_track_out, TrackOut, box);
+SAME_FIELD(mmt_track_out, TrackOut, score);
+SAME_FIELD(mmt_track_out, TrackOut, err);
+#undef SAME_FIELD
+
+const CropParam* kp(const mmt_crop_param* p) { return reinterpret_cast<const CropParam*>(p); }
+CropParam* kp(mmt_crop_param* p) { return reinterpret_cast<CropParam*>(p); }
+SeqState* ks(mmt_seq_state* p) { return reinterpret_cast<SeqState*>(p); }
+TrackOut* ko(mmt_track_out* p) { return reinterpret_cast<TrackOut*>(p); }
+
+// one int of device (or pinned) memory, read back; false: the copy failed
+bool read_int(const int* dev, int& v) { return hipMemcpy(&v, dev, sizeof(int), hipMemcpyDefault) == hipSuccess; }
+
+// the ring of an operator-level call: its fields, and the counter read back (`which`: ctr or cur) within [0, kring);
+// entry: that counter
+int check_ring(const mmt_ring_args& r, const int* which, int rows, int& entry) {
+  if (!r.params || !r.ctr || !r.cur || !which || r.kring < 1 || r.pitch < rows) return MMT_E_ARG;
+  if (!read_int(which, entry)) return MMT_E_HIP;
+  return entry < 0 || entry >= r.kring ? MMT_E_ARG : MMT_OK;
+}
+
+RingArgs to_ring(const mmt_ring_args& r) {
+  return RingArgs{kp(r.params), ko(r.outs), r.ctr, r.cur, r.kring, r.pitch};
+}
+
+// the frame fields of n descriptors, read back: a frame the kernel can index (C: the launch's channels, 0: 3 or 6)
+int check_frames(const mmt_crop_param* dev, int n, int C, bool geometry_too) {
+  std::vector<mmt_crop_param> h(n);
+  if (hipMemcpy(h.data(), dev, (size_t)n * sizeof(mmt_crop_param), hipMemcpyDefault) != hipSuccess) return MMT_E_HIP;
+  for (const mmt_crop_param& p : h) {
+    if (!p.frame || p.H < 2 || p.W < 2 || (C ? p.C != C : (p.C != 3 && p.C != 6)) || p.stride < (int64_t)p.W * p.C)
+      return MMT_E_ARG;
+    if (geometry_too && (p.crop_sz < 1 || p.crop_sz > 1000000 || std::abs((int64_t)p.x1) > (1 << 28) ||
+                         std::abs((int64_t)p.y1) > (1 << 28)))
+      return MMT_E_ARG;
+  }
+  return MMT_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mmt_crop_geometry_host(const double box[4], double factor, int out_sz, int* x1, int* y1, int* crop_sz,
+                           double* rf) {
+#pragma clang fp contract(off)
+  if (!box || !x1 || !y1 || !crop_sz || !rf) return MMT_E_ARG;
+  const double x = box[0], y = box[1], w = box[2], h = box[3];
+  const double cs = std::ceil(std::sqrt(w * h) * factor);
+  const int err = !(cs >= 1.0) ? MMT_E_BOX : cs > 1e6 ? MMT_E_ARG : MMT_OK;
+  if (err) {   // the harmless crop of geometry_of (imaging.hip)
+    *x1 = *y1 = 0;
+    *crop_sz = 1;
+    *rf = 1.0;
+    return err;
+  }
+  *crop_sz = (int)cs;
+  *x1 = (int)std::nearbyint(x + 0.5 * w - cs * 0.5);   // half to even, as python's round
+  *y1 = (int)std::nearbyint(y + 0.5 * h - cs * 0.5);
+  *rf = (double)out_sz / cs;
+  return MMT_OK;
+}
+
+int mmt_op_crop_geometry(mmt_crop_param* params, mmt_seq_state* state, int n, double factor, int out_sz,
+                         const mmt_ring_args* ring, int* gidx, int* slot2pos, int Lz, int Lx, void* stream) {
+  if (!params || !state || n < 1 || !(factor > 0) || out_sz < 1 || !gidx != !slot2pos ||
+      (gidx && (Lz < 0 || Lx < 1 || (int64_t)n * Lx > 0x7fffffff)))
+    return MMT_E_ARG;
+  RingArgs r{};
+  if (ring) {
+    int e;
+    const int rc = check_ring(*ring, ring->ctr, n, e);
+    if (rc) return rc;
+    r = to_ring(*ring);
+  }
+  crop_geometry(kp(params), ks(state), n, factor, out_sz, ring ? &r : nullptr, gidx, slot2pos, Lz, Lx,
+                (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_crop_patchify(const mmt_crop_args* c, const mmt_geom_args* g, void* stream) {
+  if (!c || !c->params || !c->A_rgb || c->B < 1 || c->out_sz < 16 || c->out_sz % 16 || c->out_sz > 4096 ||
+      (c->C != 3 && c->C != 6) || (c->C == 6 && (!c->A_aux || !c->A_rgb_lo != !c->A_aux_lo)) || c->row0 < 0 ||
+      c->rows_per_seq < 1 || c->row0 + (int64_t)(c->out_sz / 16) * (c->out_sz / 16) > c->rows_per_seq)
+    return MMT_E_ARG;
+  CropArgs a{};
+  const mmt_crop_param* frames = c->params;
+  if (g) {
+    if (!g->state || !(g->factor > 0) || !g->gidx != !g->slot2pos ||
+        (g->gidx && (g->Lz < 0 || g->Lx < 1 || (int64_t)c->B * g->Lx > 0x7fffffff)))
+      return MMT_E_ARG;
+    a.geom.state = ks(g->state);
+    a.geom.factor = g->factor;
+    a.geom.use_ring = g->use_ring ? 1 : 0;
+    if (g->use_ring) {
+      int e;
+      const int rc = check_ring(g->ring, g->ring.ctr, c->B, e);
+      if (rc) return rc;
+      a.geom.ring = to_ring(g->ring);
+      frames = g->ring.params + (int64_t)e * g->ring.pitch;
+    }
+    a.geom.gidx = g->gidx;
+    a.geom.slot2pos = g->slot2pos;
+    a.geom.Lz = g->Lz;
+    a.geom.Lx = g->Lx;
+  }
+  const int rc = check_frames(frames, c->B, c->C, !g);
+  if (rc) return rc;
+  a.params = kp(c->params);
+  a.B = c->B;
+  a.out_sz = c->out_sz;
+  a.C = c->C;
+  a.A_rgb = (bf16_t*)c->A_rgb;
+  a.A_aux = (bf16_t*)c->A_aux;
+  a.A_rgb_lo = (bf16_t*)c->A_rgb_lo;
+  a.A_aux_lo = (bf16_t*)c->A_aux_lo;
+  a.rows_per_seq = c->rows_per_seq;
+  a.row0 = c->row0;
+  a.dbg_patch = c->dbg_patch;
+  crop_patchify(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_decode(const mmt_decode_args* d, void* stream) {
+  if (!d || d->B < 1 || d->fs < 1 || d->fs > 1024 || !d->h4 || !d->w5 || !d->b5 || !d->hann || !d->res)
+    return MMT_E_ARG;
+  if (d->state && (!d->params || !d->out || d->search_size < 1)) return MMT_E_ARG;
+  if (d->ring_outs || d->ring_ctr) {   // the entry decode writes / advances from, read back
+    if (!d->ring_cur || d->ring_kring < 1 || (d->ring_outs && (!d->state || d->row0 < 0 || d->row0 + d->B > d->ring_pitch)))
+      return MMT_E_ARG;
+    int e;
+    if (!read_int(d->ring_cur, e)) return MMT_E_HIP;
+    if (e < 0 || e >= d->ring_kring) return MMT_E_ARG;
+  }
+  DecodeArgs a{};
+  a.B = d->B;
+  a.fs = d->fs;
+  a.h4 = d->h4;
+  a.w5 = d->w5;
+  a.b5 = d->b5;
+  a.hann = d->hann;
+  a.res = d->res;
+  a.maps = d->maps;
+  a.state = ks(d->state);
+  a.params = kp(d->params);
+  a.out = ko(d->out);
+  a.search_size = d->search_size;
+  a.ring_outs = ko(d->ring_outs);
+  a.ring_cur = d->ring_cur;
+  a.ring_pitch = d->ring_pitch;
+  a.row0 = d->row0;
+  a.ring_ctr = d->ring_ctr;
+  a.ring_kring = d->ring_kring;
+  decode(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_struct_layout(int which, size_t* out, int cap) {
+  std::vector<size_t> v;
+#define F(T, f) v.push_back(offsetof(T, f))
+  switch (which) {
+    case 0:
+      v.push_back(sizeof(mmt_crop_param));
+      F(mmt_crop_param, frame); F(mmt_crop_param, stride); F(mmt_crop_param, H); F(mmt_crop_param, W);
+      F(mmt_crop_param, C); F(mmt_crop_param, x1); F(mmt_crop_param, y1); F(mmt_crop_param, crop_sz);
+      F(mmt_crop_param, pad_);
+      break;
+    case 1:
+      v.push_back(sizeof(mmt_seq_state));
+      F(mmt_seq_state, box); F(mmt_seq_state, rf); F(mmt_seq_state, err); F(mmt_seq_state, pad_);
+      break;
+    case 2:
+      v.push_back(sizeof(mmt_track_out));
+      F(mmt_track_out, box); F(mmt_track_out, score); F(mmt_track_out, err); F(mmt_track_out, pad_);
+      break;
+    case 3:
+      v.push_back(sizeof(mmt_ring_args));
+      F(mmt_ring_args, params); F(mmt_ring_args, outs); F(mmt_ring_args, ctr); F(mmt_ring_args, cur);
+      F(mmt_ring_args, kring); F(mmt_ring_args, pitch);
+      break;
+    case 4:
+      v.push_back(sizeof(mmt_crop_args));
+      F(mmt_crop_args, params); F(mmt_crop_args, B); F(mmt_crop_args, out_sz); F(mmt_crop_args, C);
+      F(mmt_crop_args, A_rgb); F(mmt_crop_args, A_aux); F(mmt_crop_args, A_rgb_lo); F(mmt_crop_args, A_aux_lo);
+      F(mmt_crop_args, rows_per_seq); F(mmt_crop_args, row0); F(mmt_crop_args, dbg_patch);
+      break;
+    case 5:
+      v.push_back(sizeof(mmt_geom_args));
+      F(mmt_geom_args, state); F(mmt_geom_args, factor); F(mmt_geom_args, ring); F(mmt_geom_args, use_ring);
+      F(mmt_geom_args, gidx); F(mmt_geom_args, slot2pos); F(mmt_geom_args, Lz); F(mmt_geom_args, Lx);
+      break;
+    case 6:
+      v.push_back(sizeof(mmt_decode_args));
+      F(mmt_decode_args, B); F(mmt_decode_args, fs); F(mmt_decode_args, h4); F(mmt_decode_args, w5);
+      F(mmt_decode_args, b5); F(mmt_decode_args, hann); F(mmt_decode_args, res); F(mmt_decode_args, maps);
+      F(mmt_decode_args, state); F(mmt_decode_args, params); F(mmt_decode_args, out);
+      F(mmt_decode_args, search_size); F(mmt_decode_args, ring_outs); F(mmt_decode_args, ring_cur);
+      F(mmt_decode_args, ring_pitch); F(mmt_decode_args, row0); F(mmt_decode_args, ring_ctr);
+      F(mmt_decode_args, ring_kring);
+      break;
+    default:
+      return 0;
+  }
+#undef F
+  for (int i = 0; i < (int)v.size() && i < cap && out; ++i) out[i] = v[i];
+  return (int)v.size();
+}
 
 int mmt_xcorr(const float* z, const float* x, float* out, int B, int Cc, int hz, int wz, int hx, int wx, float scale,
               float bias, void* stream) {

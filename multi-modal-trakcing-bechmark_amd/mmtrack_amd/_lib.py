@@ -147,7 +147,52 @@ class MmtLnPromptArgs(ctypes.Structure):
                 ("out_scale", ctypes.c_float)]
 
 
-ABI_VERSION = 7   # include/mmtrack.h MMT_ABI_VERSION
+class MmtCropParam(ctypes.Structure):
+    _fields_ = [("frame", ctypes.c_void_p), ("stride", ctypes.c_int64), ("H", ctypes.c_int), ("W", ctypes.c_int),
+                ("C", ctypes.c_int), ("x1", ctypes.c_int), ("y1", ctypes.c_int), ("crop_sz", ctypes.c_int),
+                ("pad_", ctypes.c_int)]
+
+
+class MmtSeqState(ctypes.Structure):
+    _fields_ = [("box", ctypes.c_double * 4), ("rf", ctypes.c_double), ("err", ctypes.c_int), ("pad_", ctypes.c_int)]
+
+
+class MmtTrackOut(ctypes.Structure):
+    _fields_ = [("box", ctypes.c_double * 4), ("score", ctypes.c_float), ("err", ctypes.c_int),
+                ("pad_", ctypes.c_int * 2)]
+
+
+class MmtRingArgs(ctypes.Structure):
+    _fields_ = [("params", ctypes.c_void_p), ("outs", ctypes.c_void_p), ("ctr", ctypes.c_void_p),
+                ("cur", ctypes.c_void_p), ("kring", ctypes.c_int), ("pitch", ctypes.c_int)]
+
+
+class MmtCropArgs(ctypes.Structure):
+    _fields_ = [("params", ctypes.c_void_p), ("B", ctypes.c_int), ("out_sz", ctypes.c_int), ("C", ctypes.c_int),
+                ("A_rgb", ctypes.c_void_p), ("A_aux", ctypes.c_void_p), ("A_rgb_lo", ctypes.c_void_p),
+                ("A_aux_lo", ctypes.c_void_p), ("rows_per_seq", ctypes.c_int), ("row0", ctypes.c_int),
+                ("dbg_patch", ctypes.c_void_p)]
+
+
+class MmtGeomArgs(ctypes.Structure):
+    _fields_ = [("state", ctypes.c_void_p), ("factor", ctypes.c_double), ("ring", MmtRingArgs),
+                ("use_ring", ctypes.c_int), ("gidx", ctypes.c_void_p), ("slot2pos", ctypes.c_void_p),
+                ("Lz", ctypes.c_int), ("Lx", ctypes.c_int)]
+
+
+class MmtDecodeArgs(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("fs", ctypes.c_int), ("h4", ctypes.c_void_p), ("w5", ctypes.c_void_p),
+                ("b5", ctypes.c_void_p), ("hann", ctypes.c_void_p), ("res", ctypes.c_void_p), ("maps", ctypes.c_void_p),
+                ("state", ctypes.c_void_p), ("params", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("search_size", ctypes.c_int), ("ring_outs", ctypes.c_void_p), ("ring_cur", ctypes.c_void_p),
+                ("ring_pitch", ctypes.c_int), ("row0", ctypes.c_int), ("ring_ctr", ctypes.c_void_p),
+                ("ring_kring", ctypes.c_int)]
+
+
+# mmt_op_struct_layout's `which` of each mirror above
+STRUCT_LAYOUTS = [MmtCropParam, MmtSeqState, MmtTrackOut, MmtRingArgs, MmtCropArgs, MmtGeomArgs, MmtDecodeArgs]
+
+ABI_VERSION = 8   # include/mmtrack.h MMT_ABI_VERSION
 
 # every symbol include/mmtrack.h declares: name -> (restype, argtypes)
 _P = ctypes.c_void_p
@@ -242,6 +287,12 @@ SIGNATURES = {
     "mmt_op_prompt_expand_ln": (_I, [ctypes.POINTER(MmtLnPromptArgs), _P]),
     "mmt_prompt_fold": (_I, [_P] * 13),
     "mmt_tokens_force_config": (_I, [_I, _I]),
+    "mmt_crop_geometry_host": (_I, [ctypes.POINTER(_D), _D, _I, ctypes.POINTER(_I), ctypes.POINTER(_I),
+                                    ctypes.POINTER(_I), ctypes.POINTER(_D)]),
+    "mmt_op_crop_geometry": (_I, [_P, _P, _I, _D, _I, ctypes.POINTER(MmtRingArgs), _P, _P, _I, _I, _P]),
+    "mmt_op_crop_patchify": (_I, [ctypes.POINTER(MmtCropArgs), ctypes.POINTER(MmtGeomArgs), _P]),
+    "mmt_op_decode": (_I, [ctypes.POINTER(MmtDecodeArgs), _P]),
+    "mmt_op_struct_layout": (_I, [_I, ctypes.POINTER(ctypes.c_size_t), _I]),
 }
 
 _lib = None

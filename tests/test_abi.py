@@ -51,6 +51,23 @@ def test_dimp_state_layout_matches_binding():
     assert _lib.MmtDimpState.target_boxes.offset % 16 == 0 or _lib.MmtDimpState.target_boxes.offset % 4 == 0
 
 
+def test_frame_op_struct_layouts_match_binding():
+    """The structs of the frame-side operator entry points (crop, crop geometry, decode): the size and every field
+    offset the library was compiled with equal the ctypes mirror's, field for field (no GPU needed)."""
+    import ctypes
+    lib = _lib.load()
+    for which, cls in enumerate(_lib.STRUCT_LAYOUTS):
+        want = [ctypes.sizeof(cls)] + [getattr(cls, name).offset for name, _ in cls._fields_]
+        buf = (ctypes.c_size_t * 32)()
+        n = lib.mmt_op_struct_layout(which, buf, 32)
+        assert n == len(want), cls.__name__
+        assert list(buf[:n]) == want, cls.__name__
+    assert lib.mmt_op_struct_layout(len(_lib.STRUCT_LAYOUTS), None, 0) == 0
+    # the device records are read as arrays: no tail padding surprises
+    assert ctypes.sizeof(_lib.MmtCropParam) == 48 and ctypes.sizeof(_lib.MmtSeqState) == 48
+    assert ctypes.sizeof(_lib.MmtTrackOut) == 48
+
+
 def test_conv_launch_plan_without_gpu():
     """The f16x3 conv's host-side launch plan through mmt_conv2d_f16x3_ws_bytes (no GPU call): split-K slices
     follow the output tiles -- the 3 x 3 stride-1 patch kernel tiles 18 x 18 maps over the flattened batch (32 images:
