@@ -92,8 +92,9 @@ const char* mmt_version(void);
  * (mmt_op_layernorm_ex, mmt_op_ce_select, mmt_op_final_norm_recover, mmt_op_prompt_reduce,
  * mmt_op_prompt_expand_ln), mmt_prompt_fold and mmt_tokens_force_config.  8: operator entry points of the frame-side
  * kernels (mmt_op_crop_patchify, mmt_op_crop_geometry, mmt_op_decode), mmt_crop_geometry_host and
- * mmt_op_struct_layout. */
-#define MMT_ABI_VERSION 8
+ * mmt_op_struct_layout.  9: mmt_op_gemm_ex, the GEMM launched as the engine launches it (groups, conv A, caller's
+ * split-K workspace, deferred reduce), reporting the tile and K slices it ran. */
+#define MMT_ABI_VERSION 9
 int mmt_abi_version(void);
 /* pinned host memory that kernels read and write in place (mapped + coherent: a kernel sees the host's latest
  * writes and the host sees the kernel's after an event, with no copy launch) -- the DiMP pool's frame descriptors
@@ -456,6 +457,38 @@ int mmt_op_layernorm(const float* x, const float* w, const float* b, void* out_b
 int mmt_op_gemm_f16x3(const void* A_hi, const void* A_lo, int64_t lda, const void* W_hi, const void* W_lo, int64_t ldw,
                       const float* bias, void* C, void* C_lo, int64_t ldc, const float* R, int64_t ldr, int M, int N, int K,
                       int epi, float inv, float out_scale, int conv_hw, int conv_cin, void* hip_stream);
+/* the GEMM as the engine launches it: up to three groups of one shape in a launch (their own operands, bias, inv and
+ * out_scale), the implicit 3x3 conv A (conv_hw > 0; lda >= conv_cin: a column slice of a wider map), pos_rows of
+ * epilogue 6, conc (launches of this shape running beside each other on the chip: what the tile rules count) and the
+ * caller's own split-K workspace ws of ws_elems floats (NULL: K is never split).  split = 1: the f16x3 mode (A_lo /
+ * W_lo, and C_lo for epilogues 0, 1, 3); split = 0: bf16 operands, inv / out_scale unused.  defer_reduce = 1
+ * (epilogue 2, one group): a split-K run leaves its ks raw fp32 slabs in ws as [ks][M][N] -- no inv, no bias, C
+ * untouched -- for a consuming token kernel (mmt_row_reduce).  Arguments are checked before any HIP call (MMT_E_ARG,
+ * nothing launched).  ran (or NULL): the plan that was launched.                                                  */
+typedef struct mmt_gemm_group {   /* one group of a launch (csrc/kernels.h GemmGroup, field for field) */
+  const void *A, *A_lo;
+  int64_t lda;
+  const void *W, *W_lo;
+  int64_t ldw;
+  const float* bias;
+  void *C, *C_lo;
+  int64_t ldc;
+  const float* R;
+  int64_t ldr;
+  float inv, out_scale;
+} mmt_gemm_group;
+typedef struct mmt_gemm_ex_args {
+  mmt_gemm_group g[3];
+  int groups, M, N, K, epi, split, conv_hw, conv_cin, pos_rows, conc, defer_reduce;
+  float* ws;
+  int64_t ws_elems;
+} mmt_gemm_ex_args;
+typedef struct mmt_gemm_ran {
+  char tile[32];   /* the tile's name (csrc/gemm_plan.h), e.g. "128x192_4x2_s2_k64", "gemm128w" */
+  int ksplit;      /* K slices (1: none) */
+  int deferred;    /* 1: the slices' slabs were left in ws for the consumer */
+} mmt_gemm_ran;
+int mmt_op_gemm_ex(const mmt_gemm_ex_args* a, mmt_gemm_ran* ran, void* hip_stream);
 int mmt_op_attention_f16x3(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, int B, int N, int heads,
                            int ce_query, int ce_lens_t, float* ce_prob, float s_qkv, void* hip_stream);
 /* the mask mode's CE kernel (csrc/ce_rows.hip) on the qkv buffer attention reads: ce_prob [B][heads][N - lens_t] =
@@ -662,7 +695,7 @@ int mmt_op_decode(const mmt_decode_args* a, void* hip_stream);
 /* the layout of a struct above as this library was compiled (a binding checks its mirror): out[0] = sizeof, then the
  * offset of every field in declaration order; returns the number of values (0: unknown struct), writes at most cap.
  * which: 0 mmt_crop_param, 1 mmt_seq_state, 2 mmt_track_out, 3 mmt_ring_args, 4 mmt_crop_args, 5 mmt_geom_args,
- * 6 mmt_decode_args                                                                                              */
+ * 6 mmt_decode_args, 7 mmt_gemm_group, 8 mmt_gemm_ex_args, 9 mmt_gemm_ran                                         */
 int mmt_op_struct_layout(int which, size_t* out, int cap);
 
 #ifdef __cplusplus

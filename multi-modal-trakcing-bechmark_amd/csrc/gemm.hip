@@ -1986,7 +1986,7 @@ static void launch_plan(const GemmPlan& p, const GemmArgs& a0, int epi, hipStrea
 
 static int g_force_cfg = -1;   // tuning override (mmt_gemm_force_config), -1 = heuristic
 
-int gemm(const GemmArgs& a, int epi, hipStream_t s, const char** error) {
+GemmPlan gemm_plan_of(const GemmArgs& a, int epi) {
   static const GemmKnobs knobs = gemm_knobs_from_env();
   const GemmShape sh{a.M, a.N, a.K, a.groups, a.amode, epi, a.split, a.conc, a.ws != nullptr, a.ws_elems, a.defer_reduce};
   GemmPlan p = gemm_plan(sh, knobs, num_cus(), g_force_cfg);
@@ -1995,6 +1995,11 @@ int gemm(const GemmArgs& a, int epi, hipStream_t s, const char** error) {
   if (a.split && epi_is_bf16(epi))
     for (int i = 0; i < a.groups; ++i)
       if (!a.g[i].C_lo) p.error = "f16x3 GEMM with a 16-bit epilogue needs C_lo";
+  return p;
+}
+
+int gemm(const GemmArgs& a, int epi, hipStream_t s, const char** error) {
+  const GemmPlan p = gemm_plan_of(a, epi);
   if (error) *error = p.error;
   if (p.error) return -1;
   launch_plan(p, a, epi, s);

@@ -56,6 +56,8 @@ struct RowReduce {
 // in a.ws ([ks][M][N], one group) for the consumer to combine (RowReduce below) instead of a reduce launch
 // -1, nothing launched and *error set: no kernel runs this shape / epilogue / A mode (gemm_plan), or C_lo is missing
 int gemm(const GemmArgs& a, int epi, hipStream_t s, const char** error = nullptr);
+// the plan gemm() launches for these arguments (its own gemm_plan call: knobs, CU count, pin); error set: it launches nothing
+GemmPlan gemm_plan_of(const GemmArgs& a, int epi);
 void gemm_force_config(int cfg);   // tuning override, -1 = heuristic
 int gemm_set_stamps(void* dev_buf);  // tuning: per-block cycle stamps [blocks][4] (null: off)
 

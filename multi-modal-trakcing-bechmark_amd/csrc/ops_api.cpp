@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstdio>
 #include <vector>
 
 #include "engine.h"
@@ -112,6 +113,15 @@ static_assert(sizeof(mmt_track_out) == sizeof(TrackOut), "mmt_track_out");
 SAME_FIELD(mmt_track_out, TrackOut, box);
 SAME_FIELD(mmt_track_out, TrackOut, score);
 SAME_FIELD(mmt_track_out, TrackOut, err);
+static_assert(sizeof(mmt_gemm_group) == sizeof(GemmGroup), "mmt_gemm_group");
+SAME_FIELD(mmt_gemm_group, GemmGroup, A_lo);
+SAME_FIELD(mmt_gemm_group, GemmGroup, W_lo);
+SAME_FIELD(mmt_gemm_group, GemmGroup, bias);
+SAME_FIELD(mmt_gemm_group, GemmGroup, C_lo);
+SAME_FIELD(mmt_gemm_group, GemmGroup, R);
+SAME_FIELD(mmt_gemm_group, GemmGroup, ldr);
+SAME_FIELD(mmt_gemm_group, GemmGroup, inv);
+SAME_FIELD(mmt_gemm_group, GemmGroup, out_scale);
 #undef SAME_FIELD
 
 const CropParam* kp(const mmt_crop_param* p) { return reinterpret_cast<const CropParam*>(p); }
@@ -309,6 +319,24 @@ int mmt_op_struct_layout(int which, size_t* out, int cap) {
       F(mmt_decode_args, ring_pitch); F(mmt_decode_args, row0); F(mmt_decode_args, ring_ctr);
       F(mmt_decode_args, ring_kring);
       break;
+    case 7:
+      v.push_back(sizeof(mmt_gemm_group));
+      F(mmt_gemm_group, A); F(mmt_gemm_group, A_lo); F(mmt_gemm_group, lda); F(mmt_gemm_group, W);
+      F(mmt_gemm_group, W_lo); F(mmt_gemm_group, ldw); F(mmt_gemm_group, bias); F(mmt_gemm_group, C);
+      F(mmt_gemm_group, C_lo); F(mmt_gemm_group, ldc); F(mmt_gemm_group, R); F(mmt_gemm_group, ldr);
+      F(mmt_gemm_group, inv); F(mmt_gemm_group, out_scale);
+      break;
+    case 8:
+      v.push_back(sizeof(mmt_gemm_ex_args));
+      F(mmt_gemm_ex_args, g); F(mmt_gemm_ex_args, groups); F(mmt_gemm_ex_args, M); F(mmt_gemm_ex_args, N);
+      F(mmt_gemm_ex_args, K); F(mmt_gemm_ex_args, epi); F(mmt_gemm_ex_args, split); F(mmt_gemm_ex_args, conv_hw);
+      F(mmt_gemm_ex_args, conv_cin); F(mmt_gemm_ex_args, pos_rows); F(mmt_gemm_ex_args, conc);
+      F(mmt_gemm_ex_args, defer_reduce); F(mmt_gemm_ex_args, ws); F(mmt_gemm_ex_args, ws_elems);
+      break;
+    case 9:
+      v.push_back(sizeof(mmt_gemm_ran));
+      F(mmt_gemm_ran, tile); F(mmt_gemm_ran, ksplit); F(mmt_gemm_ran, deferred);
+      break;
     default:
       return 0;
   }
@@ -416,6 +444,50 @@ int mmt_op_gemm_f16x3(const void* A_hi, const void* A_lo, int64_t lda, const voi
   a.conv_cin = conv_cin;
   a.pos_rows = 1;
   if (gemm(a, epi, (hipStream_t)stream) < 0) return MMT_E_ARG;   // no kernel for this shape / epilogue: nothing ran
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_op_gemm_ex(const mmt_gemm_ex_args* x, mmt_gemm_ran* ran, void* stream) {
+  if (!x || x->groups < 1 || x->groups > 3 || x->M <= 0 || x->N <= 0 || x->K <= 0 || x->K % 64 || x->N % 32 ||
+      x->epi < 0 || x->epi > 6 || x->ws_elems < 0 || (x->ws_elems > 0 && !x->ws))
+    return MMT_E_ARG;
+  const int epi = x->epi;
+  const bool out16 = epi == EPI_BF16 || epi == EPI_GELU_BF16 || epi == EPI_RELU_BF16;
+  const bool has_r = epi == EPI_RESID_F32 || epi == EPI_POS_F32;
+  const bool conv = x->conv_hw > 0;
+  if (conv && (x->conv_cin <= 0 || x->conv_cin % 64 || x->K != 9 * x->conv_cin ||
+               (epi != EPI_RELU_BF16 && epi != EPI_RELU_F32)))
+    return MMT_E_ARG;
+  GemmArgs a{};
+  for (int i = 0; i < x->groups; ++i) {
+    const mmt_gemm_group& g = x->g[i];
+    if (!g.A || !g.W || !g.C || (x->split && (!g.A_lo || !g.W_lo || (out16 && !g.C_lo))) || (has_r && !g.R) ||
+        (conv && g.lda < x->conv_cin))
+      return MMT_E_ARG;
+    a.g[i] = GemmGroup{(const bf16_t*)g.A, (const bf16_t*)g.A_lo, g.lda, (const bf16_t*)g.W, (const bf16_t*)g.W_lo,
+                       g.ldw, g.bias, g.C, g.C_lo, g.ldc, g.R, g.ldr, g.inv, g.out_scale};
+  }
+  a.groups = x->groups;
+  a.M = x->M;
+  a.N = x->N;
+  a.K = x->K;
+  a.amode = conv ? A_CONV3 : A_DENSE;
+  a.conv_hw = x->conv_hw;
+  a.conv_cin = x->conv_cin;
+  a.pos_rows = x->pos_rows > 0 ? x->pos_rows : 1;
+  a.split = x->split ? 1 : 0;
+  a.ws = x->ws_elems > 0 ? x->ws : nullptr;
+  a.ws_elems = x->ws_elems;
+  a.zero = a.split ? nullptr : op_zero_page();
+  a.defer_reduce = x->defer_reduce ? 1 : 0;
+  a.conc = x->conc;
+  const GemmPlan p = gemm_plan_of(a, epi);   // the plan gemm() launches below
+  if (gemm(a, epi, (hipStream_t)stream) < 0) return MMT_E_ARG;   // no kernel for this shape / epilogue: nothing ran
+  if (ran) {
+    snprintf(ran->tile, sizeof ran->tile, "%s", gemm_tile_name(p.tile));
+    ran->ksplit = p.ksplit;
+    ran->deferred = p.defer ? 1 : 0;
+  }
   return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
 }
 

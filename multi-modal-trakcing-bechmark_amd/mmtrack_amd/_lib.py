@@ -189,10 +189,29 @@ class MmtDecodeArgs(ctypes.Structure):
                 ("ring_kring", ctypes.c_int)]
 
 
-# mmt_op_struct_layout's `which` of each mirror above
-STRUCT_LAYOUTS = [MmtCropParam, MmtSeqState, MmtTrackOut, MmtRingArgs, MmtCropArgs, MmtGeomArgs, MmtDecodeArgs]
+class MmtGemmGroup(ctypes.Structure):
+    _fields_ = [("A", ctypes.c_void_p), ("A_lo", ctypes.c_void_p), ("lda", ctypes.c_int64), ("W", ctypes.c_void_p),
+                ("W_lo", ctypes.c_void_p), ("ldw", ctypes.c_int64), ("bias", ctypes.c_void_p), ("C", ctypes.c_void_p),
+                ("C_lo", ctypes.c_void_p), ("ldc", ctypes.c_int64), ("R", ctypes.c_void_p), ("ldr", ctypes.c_int64),
+                ("inv", ctypes.c_float), ("out_scale", ctypes.c_float)]
 
-ABI_VERSION = 8   # include/mmtrack.h MMT_ABI_VERSION
+
+class MmtGemmExArgs(ctypes.Structure):
+    _fields_ = [("g", MmtGemmGroup * 3), ("groups", ctypes.c_int), ("M", ctypes.c_int), ("N", ctypes.c_int),
+                ("K", ctypes.c_int), ("epi", ctypes.c_int), ("split", ctypes.c_int), ("conv_hw", ctypes.c_int),
+                ("conv_cin", ctypes.c_int), ("pos_rows", ctypes.c_int), ("conc", ctypes.c_int),
+                ("defer_reduce", ctypes.c_int), ("ws", ctypes.c_void_p), ("ws_elems", ctypes.c_int64)]
+
+
+class MmtGemmRan(ctypes.Structure):
+    _fields_ = [("tile", ctypes.c_char * 32), ("ksplit", ctypes.c_int), ("deferred", ctypes.c_int)]
+
+
+# mmt_op_struct_layout's `which` of each mirror above
+STRUCT_LAYOUTS = [MmtCropParam, MmtSeqState, MmtTrackOut, MmtRingArgs, MmtCropArgs, MmtGeomArgs, MmtDecodeArgs,
+                  MmtGemmGroup, MmtGemmExArgs, MmtGemmRan]
+
+ABI_VERSION = 9   # include/mmtrack.h MMT_ABI_VERSION
 
 # every symbol include/mmtrack.h declares: name -> (restype, argtypes)
 _P = ctypes.c_void_p
@@ -275,6 +294,7 @@ SIGNATURES = {
     "mmt_op_layernorm": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "mmt_op_gemm_f16x3": (_I, [_P, _P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I, _I, _I, _I, _F, _F, _I, _I,
                                _P]),
+    "mmt_op_gemm_ex": (_I, [ctypes.POINTER(MmtGemmExArgs), ctypes.POINTER(MmtGemmRan), _P]),
     "mmt_op_attention_f16x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _F, _P]),
     "mmt_op_ce_rows": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
     "mmt_op_ce_rows_f16x3": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _P, _F, _P]),

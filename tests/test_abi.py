@@ -68,6 +68,53 @@ def test_frame_op_struct_layouts_match_binding():
     assert ctypes.sizeof(_lib.MmtTrackOut) == 48
 
 
+def _gemm_ex_args(**over):
+    """A valid one-group f16x3 conv launch (conv2's shape) over dummy non-null pointers; `over` replaces fields of the
+    launch, or with a g_ prefix of its groups."""
+    a = _lib.MmtGemmExArgs()
+    a.groups, a.M, a.N, a.K, a.epi, a.split = 1, 256, 128, 2304, 3, 1
+    a.conv_hw, a.conv_cin, a.pos_rows, a.conc, a.defer_reduce = 16, 256, 1, 0, 0
+    a.ws, a.ws_elems = 0x1000, 1 << 20
+    for g in a.g:
+        g.A = g.A_lo = g.W = g.W_lo = g.bias = g.C = g.C_lo = g.R = 0x1000
+        g.lda, g.ldw, g.ldc, g.ldr, g.inv, g.out_scale = 768, 2304, 128, 128, 1.0, 1.0
+    for k, v in over.items():
+        if k.startswith("g_"):
+            for g in a.g:
+                setattr(g, k[2:], v)
+        else:
+            setattr(a, k, v)
+    return a
+
+
+def test_gemm_ex_rejects_bad_arguments_without_gpu():
+    """mmt_op_gemm_ex checks its arguments before any HIP call: every rejected launch below returns MMT_E_ARG over
+    dummy pointers on a machine without a GPU (a launch that got past the checks would report MMT_E_HIP or die)."""
+    import ctypes
+    lib = _lib.load()
+    ran = _lib.MmtGemmRan()
+    dense = dict(conv_hw=0, conv_cin=0, K=768, N=768)
+    bad = [
+        dict(groups=0), dict(groups=4), dict(M=0), dict(N=0), dict(K=0), dict(M=-5), dict(K=2304 + 32, conv_hw=0),
+        dict(N=48), dict(epi=-1), dict(epi=7),
+        dict(g_A=None), dict(g_W=None), dict(g_C=None),
+        dict(g_A_lo=None), dict(g_W_lo=None),                  # f16x3 operands without their low halves
+        dict(g_C_lo=None),                                     # a split 16-bit epilogue without its low plane
+        dict(dense, epi=0, g_C_lo=None), dict(dense, epi=1, g_C_lo=None),
+        dict(dense, epi=2, g_R=None), dict(dense, epi=6, g_R=None, pos_rows=4),
+        dict(conv_cin=288, K=9 * 288),                         # conv: conv_cin % 64
+        dict(conv_cin=128),                                    # conv: K != 9 conv_cin
+        dict(epi=0), dict(epi=2), dict(epi=4),                 # conv: not a ReLU epilogue
+        dict(g_lda=128),                                       # conv: lda < conv_cin
+        dict(ws_elems=-1), dict(ws=None),                      # ws_elems > 0 without a workspace
+    ]
+    for over in bad:
+        a = _gemm_ex_args(**over)
+        assert lib.mmt_op_gemm_ex(ctypes.byref(a), ctypes.byref(ran), None) == _lib.MMT_E_ARG, over
+        assert lib.mmt_op_gemm_ex(ctypes.byref(a), None, None) == _lib.MMT_E_ARG, over   # a null `ran` is accepted
+    assert lib.mmt_op_gemm_ex(None, None, None) == _lib.MMT_E_ARG
+
+
 def test_conv_launch_plan_without_gpu():
     """The f16x3 conv's host-side launch plan through mmt_conv2d_f16x3_ws_bytes (no GPU call): split-K slices
     follow the output tiles -- the 3 x 3 stride-1 patch kernel tiles 18 x 18 maps over the flattened batch (32 images:
