@@ -93,8 +93,10 @@ const char* mmt_version(void);
  * mmt_op_prompt_expand_ln), mmt_prompt_fold and mmt_tokens_force_config.  8: operator entry points of the frame-side
  * kernels (mmt_op_crop_patchify, mmt_op_crop_geometry, mmt_op_decode), mmt_crop_geometry_host and
  * mmt_op_struct_layout.  9: mmt_op_gemm_ex, the GEMM launched as the engine launches it (groups, conv A, caller's
- * split-K workspace, deferred reduce), reporting the tile and K slices it ran. */
-#define MMT_ABI_VERSION 9
+ * split-K workspace, deferred reduce), reporting the tile and K slices it ran.  10: the SiamFC tracker state
+ * machine on the device (mmt_siamfc_pool_crop, mmt_xcorr_nhwc_group, mmt_siamfc_pool_update; mmt_op_struct_layout
+ * 10 / 11 / 12 = mmt_siamfc_state / _params / _result). */
+#define MMT_ABI_VERSION 10
 int mmt_abi_version(void);
 /* pinned host memory that kernels read and write in place (mapped + coherent: a kernel sees the host's latest
  * writes and the host sees the kernel's after an event, with no copy launch) -- the DiMP pool's frame descriptors
@@ -430,6 +432,63 @@ int mmt_dimp_optimize_strided(const float* feat, int64_t feat_img_stride, int64_
                               int64_t sw_img_stride, int64_t sw_seq_stride, const mmt_dimp_params* p, int num_iter,
                               void* workspace, size_t ws_bytes, void* hip_stream);
 
+/* ---- SiamFC tracker state machine on the device (csrc/siamfc_pool.hip), batched over sequences ------------
+ * TrackerSiamFC.update (mmtrack_amd/siamfc.py) with the per-sequence state in device memory, so a frame of n
+ * sequences is: mmt_siamfc_pool_crop (the scale pyramid's windows from the state, each sequence's own frame) ->
+ * the AlexNet backbone over n * scale_num crops -> mmt_xcorr_nhwc_group (a sequence's scales share its exemplar)
+ * -> mmt_siamfc_pool_update (mmt_siamfc_response's selection per sequence, then the state law and the result
+ * record).  Nothing crosses to the host before the next frame is launched; every stage is the sequential
+ * tracker's own device code, so a pool of any size reproduces its decisions bit for bit.  Arrays of structs
+ * below are device memory; frames are mmt_dimp_frame records (C >= 3, the first three channels are read; each
+ * sequence its own size).                                                                                  */
+typedef struct mmt_siamfc_state {      /* one per slot, device memory                                       */
+  double center[2];                    /* (y, x), 0-based, as TrackerSiamFC.center                          */
+  double target_sz[2];                 /* (h, w)                                                            */
+  double z_sz, x_sz;
+  int pad[3];                          /* border colour (rint of the first frame's mean colour, clipped)    */
+  int frame_num;
+} mmt_siamfc_state;
+typedef struct mmt_siamfc_params {     /* CFG of mmtrack_amd/siamfc.py                                      */
+  int scale_num;                       /* 1..8                                                              */
+  int instance_sz, response_sz, response_up, total_stride;
+  float scale_penalty;
+  double scale_factors[8], scale_lr, window_influence, hann_sum;
+} mmt_siamfc_params;
+typedef struct mmt_siamfc_result {     /* per sequence and frame                                            */
+  double box[4];                       /* x, y, w, h, 1-based as update() returns it                        */
+  float value;                         /* the windowed response maximum                                     */
+  int scale_id, row, col;
+  int err;                             /* 0, or 1: a degenerate window (below); the state was left unchanged */
+  int pad_;
+} mmt_siamfc_result;
+/* sequence i, scale s: side = rint(x_sz * scale_factors[s]) (half to even), y0 = rint(center[0] - (side - 1) / 2),
+ * x0 likewise, then mmt_siamfc_crop_nhwc's crop with the slot's pad -> out [n * scale_num][instance_sz]
+ * [instance_sz][3]; windows (device int [n][scale_num][3], or NULL) receives (y0, x0, side).  A window whose side
+ * is not finite, < 1 or > 2^20 is degenerate: its crop is zeros, its `windows` row (0, 0, 0), and
+ * mmt_siamfc_pool_update leaves the sequence's state alone (err = 1) -- the flag is that predicate of the slot's
+ * state in device memory, which both entries evaluate with the same device function.  No state value makes the
+ * kernel read outside a frame (a corner beyond +-2^30 is clamped there; a descriptor with a null pointer,
+ * H or W < 1, C < 3 or stride < W * C reads as border).  n * scale_num <= 65535, instance_sz <= 4096.        */
+int mmt_siamfc_pool_crop(const mmt_siamfc_state* states, const mmt_dimp_frame* frames, int n,
+                         const mmt_siamfc_params* params, float* out, int* windows, void* hip_stream);
+/* mmt_xcorr_nhwc where entry b uses the exemplar at z + (b / group) * z_bstride (a sequence's `group` scales
+ * share its exemplar); mmt_xcorr_nhwc's limits and, bitwise, its sums.  B <= 65535.                         */
+int mmt_xcorr_nhwc_group(const float* z, int64_t z_bstride, int group, const float* x, float* out, int B, int C,
+                         int hz, int wz, int hx, int wx, float scale, float bias, void* hip_stream);
+/* resp [n * scale_num][r][r] (r = response_sz), scratch [n * scale_num][up][up] floats (up = response_up * r),
+ * hann1d [up] doubles (device).  Per sequence: mmt_siamfc_response's selection (the same device code), then in
+ * double without contraction
+ *   d = (row - (up - 1) / 2, col - (up - 1) / 2);  d = d * total_stride / response_up;
+ *   d = d * x_sz * scale_factors[scale_id] / instance_sz;  center += d;
+ *   scale = (1 - scale_lr) * 1.0 + scale_lr * scale_factors[scale_id];
+ *   target_sz *= scale; z_sz *= scale; x_sz *= scale; frame_num += 1;
+ *   box = (center[1] + 1 - (target_sz[1] - 1) / 2, center[0] + 1 - (target_sz[0] - 1) / 2, target_sz[1], target_sz[0])
+ * The record goes to results (device) and, when host_results is non-NULL (mmt_host_alloc memory), there as well:
+ * the host reads it after an event, without a copy launch.                                                   */
+int mmt_siamfc_pool_update(const float* resp, int n, const mmt_siamfc_params* params, const double* hann1d,
+                           float* scratch, mmt_siamfc_state* states, mmt_siamfc_result* results,
+                           mmt_siamfc_result* host_results, void* hip_stream);
+
 /* ---- operator-level entry points (device pointers; used by the parity tests and by hosts that
  *      compose their own pipelines).  epi: 0 bias->bf16, 1 bias+GELU->bf16, 2 C(f32) = R + acc + bias,
  *      3 bias+ReLU->bf16, 4 bias->f32, 5 bias+ReLU->f32, 6 C(f32) = acc + bias + R[m % pos_rows].
@@ -695,7 +754,8 @@ int mmt_op_decode(const mmt_decode_args* a, void* hip_stream);
 /* the layout of a struct above as this library was compiled (a binding checks its mirror): out[0] = sizeof, then the
  * offset of every field in declaration order; returns the number of values (0: unknown struct), writes at most cap.
  * which: 0 mmt_crop_param, 1 mmt_seq_state, 2 mmt_track_out, 3 mmt_ring_args, 4 mmt_crop_args, 5 mmt_geom_args,
- * 6 mmt_decode_args, 7 mmt_gemm_group, 8 mmt_gemm_ex_args, 9 mmt_gemm_ran                                         */
+ * 6 mmt_decode_args, 7 mmt_gemm_group, 8 mmt_gemm_ex_args, 9 mmt_gemm_ran, 10 mmt_siamfc_state, 11 mmt_siamfc_params,
+ * 12 mmt_siamfc_result                                                                                            */
 int mmt_op_struct_layout(int which, size_t* out, int cap);
 
 #ifdef __cplusplus

@@ -6,8 +6,7 @@
 //  * decode: the CENTER head's conv5 1x1 + sigmoid/clamp (head.py:110-124, 177-201), the Hann window
 //    (vipt.py:79-80) and cal_bbox's first-occurrence argmax + gather (head.py:142-160);
 //  * xcorr: SiamFC / DiMP per-sequence cross-correlation (grouped conv2d).
-#include "cvresize.h"
-#include "kernels.h"
+#include "siamfc_dev.h"
 
 namespace mmt {
 
@@ -372,27 +371,7 @@ __global__ __launch_bounds__(256) void xcorr_nhwc_kernel(const float* __restrict
   if (p >= ho * wo) return;
   const int y = p / wo, x = p - y * wo;
   const float* xb = X + (int64_t)b * hx * wx * C;
-  float acc = 0.f;
-  if ((C & 3) == 0) {
-    const int c4 = C >> 2;
-    for (int i = 0; i < hz; ++i)
-      for (int j = 0; j < wz; ++j) {
-        const float4* xr = reinterpret_cast<const float4*>(xb + ((int64_t)(y + i) * wx + x + j) * C);
-        const float4* zr = reinterpret_cast<const float4*>(zsh + (i * wz + j) * C);
-        for (int c = lane; c < c4; c += 64) {
-          const float4 u = xr[c], v = zr[c];
-          acc += u.x * v.x + u.y * v.y + u.z * v.z + u.w * v.w;
-        }
-      }
-  } else {
-    for (int i = 0; i < hz; ++i)
-      for (int j = 0; j < wz; ++j) {
-        const float* xr = xb + ((int64_t)(y + i) * wx + x + j) * C;
-        const float* zr = zsh + (i * wz + j) * C;
-        for (int c = lane; c < C; c += 64) acc += xr[c] * zr[c];
-      }
-  }
-  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  const float acc = xcorr_nhwc_pixel(xb, zsh, C, hz, wz, wx, y, x, lane);   // siamfc_dev.h
   if (lane == 0) out[(int64_t)b * ho * wo + p] = acc * scale + bias;
 }
 

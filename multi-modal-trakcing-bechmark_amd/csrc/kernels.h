@@ -307,4 +307,42 @@ struct SiamRespArgs {
 };
 void siamfc_response(const SiamRespArgs& a, hipStream_t s);
 
+// ---- SiamFC pool (siamfc_pool.hip): the tracker state on the device, n sequences per launch.  The structs are
+// include/mmtrack.h's mmt_siamfc_state / _params / _result, field for field (ops_api.cpp asserts it).
+struct SiamState {
+  double center[2], target_sz[2];  // (y, x) 0-based, (h, w)
+  double z_sz, x_sz;
+  int pad[3];                      // border colour
+  int frame_num;
+};
+struct SiamParams {
+  int scale_num;
+  int instance_sz, response_sz, response_up, total_stride;
+  float scale_penalty;
+  double scale_factors[8], scale_lr, window_influence, hann_sum;
+};
+struct SiamResult {
+  double box[4];                   // x, y, w, h, 1-based
+  float value;
+  int scale_id, row, col;
+  int err;                         // 1: a degenerate window, the state was left unchanged
+  int pad_;
+};
+struct SiamFrame {                 // mmt_dimp_frame
+  const uint8_t* data;
+  int64_t stride;
+  int H, W, C, pad_;
+};
+// the instance pyramid of n sequences from their device states: out [n * scale_num][instance_sz][instance_sz][3];
+// windows (or null) [n][scale_num][3] = y0, x0, side
+void siamfc_pool_crop(const SiamState* states, const SiamFrame* frames, int n, const SiamParams& p, float* out,
+                      int* windows, hipStream_t s);
+// xcorr_nhwc where entry b reads the exemplar at Z + (b / group) * z_bstride (xcorr_nhwc's layout and bits)
+void xcorr_nhwc_group(const float* Z, int64_t z_bstride, int group, const float* X, float* out, int B, int C, int hz,
+                      int wz, int hx, int wx, float scale, float bias, hipStream_t s);
+// siamfc_response per sequence (resp [n * scale_num][r][r], scratch [n * scale_num][up][up]), then the state law of
+// TrackerSiamFC.update and the result record (also to host_results when non-null: device-visible pinned memory)
+void siamfc_pool_update(const float* resp, int n, const SiamParams& p, const double* hann1d, float* scratch,
+                        SiamState* states, SiamResult* results, SiamResult* host_results, hipStream_t s);
+
 }  // namespace mmt

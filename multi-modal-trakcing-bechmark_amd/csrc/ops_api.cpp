@@ -122,7 +122,46 @@ SAME_FIELD(mmt_gemm_group, GemmGroup, R);
 SAME_FIELD(mmt_gemm_group, GemmGroup, ldr);
 SAME_FIELD(mmt_gemm_group, GemmGroup, inv);
 SAME_FIELD(mmt_gemm_group, GemmGroup, out_scale);
+static_assert(sizeof(mmt_siamfc_state) == sizeof(SiamState) && sizeof(mmt_siamfc_state) == 64, "mmt_siamfc_state");
+SAME_FIELD(mmt_siamfc_state, SiamState, center);
+SAME_FIELD(mmt_siamfc_state, SiamState, target_sz);
+SAME_FIELD(mmt_siamfc_state, SiamState, z_sz);
+SAME_FIELD(mmt_siamfc_state, SiamState, x_sz);
+SAME_FIELD(mmt_siamfc_state, SiamState, pad);
+SAME_FIELD(mmt_siamfc_state, SiamState, frame_num);
+static_assert(sizeof(mmt_siamfc_params) == sizeof(SiamParams), "mmt_siamfc_params");
+SAME_FIELD(mmt_siamfc_params, SiamParams, scale_num);
+SAME_FIELD(mmt_siamfc_params, SiamParams, instance_sz);
+SAME_FIELD(mmt_siamfc_params, SiamParams, response_sz);
+SAME_FIELD(mmt_siamfc_params, SiamParams, response_up);
+SAME_FIELD(mmt_siamfc_params, SiamParams, total_stride);
+SAME_FIELD(mmt_siamfc_params, SiamParams, scale_penalty);
+SAME_FIELD(mmt_siamfc_params, SiamParams, scale_factors);
+SAME_FIELD(mmt_siamfc_params, SiamParams, scale_lr);
+SAME_FIELD(mmt_siamfc_params, SiamParams, window_influence);
+SAME_FIELD(mmt_siamfc_params, SiamParams, hann_sum);
+static_assert(sizeof(mmt_siamfc_result) == sizeof(SiamResult), "mmt_siamfc_result");
+SAME_FIELD(mmt_siamfc_result, SiamResult, box);
+SAME_FIELD(mmt_siamfc_result, SiamResult, value);
+SAME_FIELD(mmt_siamfc_result, SiamResult, scale_id);
+SAME_FIELD(mmt_siamfc_result, SiamResult, row);
+SAME_FIELD(mmt_siamfc_result, SiamResult, col);
+SAME_FIELD(mmt_siamfc_result, SiamResult, err);
+static_assert(sizeof(mmt_dimp_frame) == sizeof(SiamFrame), "mmt_dimp_frame");
+SAME_FIELD(mmt_dimp_frame, SiamFrame, data);
+SAME_FIELD(mmt_dimp_frame, SiamFrame, stride);
+SAME_FIELD(mmt_dimp_frame, SiamFrame, H);
+SAME_FIELD(mmt_dimp_frame, SiamFrame, W);
+SAME_FIELD(mmt_dimp_frame, SiamFrame, C);
 #undef SAME_FIELD
+
+// the fields of mmt_siamfc_params a pooled SiamFC launch sizes its grid and its indexing from
+bool siamfc_params_ok(const mmt_siamfc_params* p, int n) {
+  return p && n > 0 && p->scale_num >= 1 && p->scale_num <= 8 && (int64_t)n * p->scale_num <= 65535 &&
+         p->instance_sz >= 1 && p->instance_sz <= 4096 && p->response_sz >= 2 && p->response_sz <= 256 &&
+         p->response_up >= 1 && (int64_t)p->response_up * p->response_sz <= 8192 && p->total_stride >= 1 &&
+         p->hann_sum > 0;
+}
 
 const CropParam* kp(const mmt_crop_param* p) { return reinterpret_cast<const CropParam*>(p); }
 CropParam* kp(mmt_crop_param* p) { return reinterpret_cast<CropParam*>(p); }
@@ -337,6 +376,23 @@ int mmt_op_struct_layout(int which, size_t* out, int cap) {
       v.push_back(sizeof(mmt_gemm_ran));
       F(mmt_gemm_ran, tile); F(mmt_gemm_ran, ksplit); F(mmt_gemm_ran, deferred);
       break;
+    case 10:
+      v.push_back(sizeof(mmt_siamfc_state));
+      F(mmt_siamfc_state, center); F(mmt_siamfc_state, target_sz); F(mmt_siamfc_state, z_sz); F(mmt_siamfc_state, x_sz);
+      F(mmt_siamfc_state, pad); F(mmt_siamfc_state, frame_num);
+      break;
+    case 11:
+      v.push_back(sizeof(mmt_siamfc_params));
+      F(mmt_siamfc_params, scale_num); F(mmt_siamfc_params, instance_sz); F(mmt_siamfc_params, response_sz);
+      F(mmt_siamfc_params, response_up); F(mmt_siamfc_params, total_stride); F(mmt_siamfc_params, scale_penalty);
+      F(mmt_siamfc_params, scale_factors); F(mmt_siamfc_params, scale_lr); F(mmt_siamfc_params, window_influence);
+      F(mmt_siamfc_params, hann_sum);
+      break;
+    case 12:
+      v.push_back(sizeof(mmt_siamfc_result));
+      F(mmt_siamfc_result, box); F(mmt_siamfc_result, value); F(mmt_siamfc_result, scale_id); F(mmt_siamfc_result, row);
+      F(mmt_siamfc_result, col); F(mmt_siamfc_result, err); F(mmt_siamfc_result, pad_);
+      break;
     default:
       return 0;
   }
@@ -390,6 +446,35 @@ int mmt_siamfc_response(const float* resp, int n, int r, int up, float scale_pen
   a.scratch = scratch;
   a.result = result;
   siamfc_response(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+// ---- SiamFC pool (siamfc_pool.hip): every argument is checked before any HIP call
+int mmt_siamfc_pool_crop(const mmt_siamfc_state* states, const mmt_dimp_frame* frames, int n,
+                         const mmt_siamfc_params* params, float* out, int* windows, void* stream) {
+  if (!states || !frames || !out || !siamfc_params_ok(params, n)) return MMT_E_ARG;
+  siamfc_pool_crop(reinterpret_cast<const SiamState*>(states), reinterpret_cast<const SiamFrame*>(frames), n,
+                   *reinterpret_cast<const SiamParams*>(params), out, windows, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_xcorr_nhwc_group(const float* z, int64_t z_bstride, int group, const float* x, float* out, int B, int Cc,
+                         int hz, int wz, int hx, int wx, float scale, float bias, void* stream) {
+  if (!z || !x || !out || B <= 0 || group < 1 || Cc <= 0 || hz <= 0 || wz <= 0 || hx < hz || wx < wz || z_bstride < 0 ||
+      (int64_t)hz * wz * Cc > 16384 || B > 65535 ||
+      ((Cc & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(z) | (uintptr_t)z_bstride * 4) & 15)))
+    return MMT_E_ARG;
+  xcorr_nhwc_group(z, z_bstride, group, x, out, B, Cc, hz, wz, hx, wx, scale, bias, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
+}
+
+int mmt_siamfc_pool_update(const float* resp, int n, const mmt_siamfc_params* params, const double* hann1d,
+                           float* scratch, mmt_siamfc_state* states, mmt_siamfc_result* results,
+                           mmt_siamfc_result* host_results, void* stream) {
+  if (!resp || !hann1d || !scratch || !states || !results || !siamfc_params_ok(params, n)) return MMT_E_ARG;
+  siamfc_pool_update(resp, n, *reinterpret_cast<const SiamParams*>(params), hann1d, scratch,
+                     reinterpret_cast<SiamState*>(states), reinterpret_cast<SiamResult*>(results),
+                     reinterpret_cast<SiamResult*>(host_results), (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? MMT_OK : MMT_E_HIP;
 }
 

@@ -7,8 +7,7 @@
 //  * siamfc_response: the post-correlation step of TrackerSiamFC.update -- INTER_CUBIC x16 upsampling
 //    of every scale's 17x17 response, scale penalty, first-max scale selection, min/sum normalisation,
 //    cosine-window blend in double, first-occurrence argmax.
-#include "cvresize.h"
-#include "kernels.h"
+#include "siamfc_dev.h"
 
 namespace mmt {
 
@@ -41,89 +40,15 @@ void siamfc_crop(const SiamCropArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(siamfc_crop_kernel, dim3((a.out_sz * a.out_sz + 255) / 256, a.n), dim3(256), 0, s, a);
 }
 
-constexpr int RT = 1024;
-
-__device__ __forceinline__ float block_reduce_f(float v, float* red, bool is_max, bool is_min) {
-  const int t = threadIdx.x;
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float u = __shfl_xor(v, o, 64);
-    v = is_max ? fmaxf(v, u) : (is_min ? fminf(v, u) : v + u);
-  }
-  __syncthreads();
-  if ((t & 63) == 0) red[t >> 6] = v;
-  __syncthreads();
-  if (t < 64) {
-    v = t < RT / 64 ? red[t] : (is_max ? -INFINITY : (is_min ? INFINITY : 0.f));
-    for (int o = 32; o >= 1; o >>= 1) {
-      const float u = __shfl_xor(v, o, 64);
-      v = is_max ? fmaxf(v, u) : (is_min ? fminf(v, u) : v + u);
-    }
-    if (t == 0) red[RT / 64] = v;
-  }
-  __syncthreads();
-  return red[RT / 64];
-}
-
 __global__ __launch_bounds__(RT) void siamfc_response_kernel(const SiamRespArgs a) {
-#pragma clang fp contract(off)   // numpy's separate float32 / float64 roundings
-  __shared__ float red[RT / 64 + 1];
-  __shared__ double dv[RT];
-  __shared__ int di[RT];
-  __shared__ float smax[8];
-  const int t = threadIdx.x, U = a.up, UU = U * U, mid = a.n / 2;
-  // 1. upsample every scale, penalise the off-centre scales, per-scale max
-  for (int s = 0; s < a.n; ++s) {
-    const float* src = a.resp + (int64_t)s * a.r * a.r;
-    float* dst = a.scratch + (int64_t)s * UU;
-    float m = -INFINITY;
-    for (int i = t; i < UU; i += RT) {
-      const int oy = i / U, ox = i - oy * U;
-      float v = cv_cubic_f32(src, a.r, U, oy, ox);
-      if (s != mid) v = __fmul_rn(v, a.penalty);
-      dst[i] = v;
-      m = fmaxf(m, v);
-    }
-    m = block_reduce_f(m, red, true, false);
-    if (t == 0) smax[s] = m;
-  }
-  __syncthreads();
-  int sid = 0;
-  for (int s = 1; s < a.n; ++s)
-    if (smax[s] > smax[sid]) sid = s;
-  const float* r = a.scratch + (int64_t)sid * UU;
-  // 2. response -= min; response /= sum + 1e-16
-  float mn = INFINITY;
-  for (int i = t; i < UU; i += RT) mn = fminf(mn, r[i]);
-  mn = block_reduce_f(mn, red, false, true);
-  float sm = 0.f;
-  for (int i = t; i < UU; i += RT) sm += __fsub_rn(r[i], mn);
-  sm = block_reduce_f(sm, red, false, false);
-  const float div = (float)((double)sm + 1e-16);
-  // 3. (1 - wi) * response + wi * hann (double), first-occurrence argmax
-  double best = -1e300;
-  int bi = 0x7fffffff;
-  for (int i = t; i < UU; i += RT) {
-    const int y = i / U, x = i - y * U;
-    const float nv = __fdiv_rn(__fsub_rn(r[i], mn), div);
-    const double v = (double)__fmul_rn(a.one_minus_wi, nv) + a.wi * ((a.hann1d[y] * a.hann1d[x]) / a.hann_sum);
-    if (v > best) { best = v; bi = i; }
-  }
-  dv[t] = best;
-  di[t] = bi;
-  __syncthreads();
-  for (int st = RT / 2; st > 0; st >>= 1) {
-    if (t < st) {
-      const double v2 = dv[t + st];
-      const int i2 = di[t + st];
-      if (v2 > dv[t] || (v2 == dv[t] && i2 < di[t])) { dv[t] = v2; di[t] = i2; }
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
+  int sid, idx;
+  double val;
+  siamfc_response_select(a, sid, idx, val);   // siamfc_dev.h: shared with the pooled update (siamfc_pool.hip)
+  if (threadIdx.x == 0) {
     a.result[0] = (float)sid;
-    a.result[1] = (float)(di[0] / U);
-    a.result[2] = (float)(di[0] % U);
-    a.result[3] = (float)dv[0];
+    a.result[1] = (float)(idx / a.up);
+    a.result[2] = (float)(idx % a.up);
+    a.result[3] = (float)val;
   }
 }
 

@@ -207,11 +207,28 @@ class MmtGemmRan(ctypes.Structure):
     _fields_ = [("tile", ctypes.c_char * 32), ("ksplit", ctypes.c_int), ("deferred", ctypes.c_int)]
 
 
+class MmtSiamfcState(ctypes.Structure):
+    _fields_ = [("center", ctypes.c_double * 2), ("target_sz", ctypes.c_double * 2), ("z_sz", ctypes.c_double),
+                ("x_sz", ctypes.c_double), ("pad", ctypes.c_int * 3), ("frame_num", ctypes.c_int)]
+
+
+class MmtSiamfcParams(ctypes.Structure):
+    _fields_ = [("scale_num", ctypes.c_int), ("instance_sz", ctypes.c_int), ("response_sz", ctypes.c_int),
+                ("response_up", ctypes.c_int), ("total_stride", ctypes.c_int), ("scale_penalty", ctypes.c_float),
+                ("scale_factors", ctypes.c_double * 8), ("scale_lr", ctypes.c_double),
+                ("window_influence", ctypes.c_double), ("hann_sum", ctypes.c_double)]
+
+
+class MmtSiamfcResult(ctypes.Structure):
+    _fields_ = [("box", ctypes.c_double * 4), ("value", ctypes.c_float), ("scale_id", ctypes.c_int),
+                ("row", ctypes.c_int), ("col", ctypes.c_int), ("err", ctypes.c_int), ("pad_", ctypes.c_int)]
+
+
 # mmt_op_struct_layout's `which` of each mirror above
 STRUCT_LAYOUTS = [MmtCropParam, MmtSeqState, MmtTrackOut, MmtRingArgs, MmtCropArgs, MmtGeomArgs, MmtDecodeArgs,
-                  MmtGemmGroup, MmtGemmExArgs, MmtGemmRan]
+                  MmtGemmGroup, MmtGemmExArgs, MmtGemmRan, MmtSiamfcState, MmtSiamfcParams, MmtSiamfcResult]
 
-ABI_VERSION = 9   # include/mmtrack.h MMT_ABI_VERSION
+ABI_VERSION = 10   # include/mmtrack.h MMT_ABI_VERSION
 
 # every symbol include/mmtrack.h declares: name -> (restype, argtypes)
 _P = ctypes.c_void_p
@@ -248,6 +265,9 @@ SIGNATURES = {
     "mmt_siamfc_crop_nhwc": (_I, [_P, _I, _I, _I, ctypes.c_int64, _I, _P, _P, _P, _P, _I, _P, _P]),
     "mmt_xcorr_nhwc": (_I, [_P, ctypes.c_int64, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
     "mmt_siamfc_response": (_I, [_P, _I, _I, _I, ctypes.c_float, ctypes.c_double, _P, ctypes.c_double, _P, _P, _P]),
+    "mmt_siamfc_pool_crop": (_I, [_P, _P, _I, ctypes.POINTER(MmtSiamfcParams), _P, _P, _P]),
+    "mmt_xcorr_nhwc_group": (_I, [_P, _I64, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
+    "mmt_siamfc_pool_update": (_I, [_P, _I, ctypes.POINTER(MmtSiamfcParams), _P, _P, _P, _P, _P, _P]),
     "mmt_rgbd_workspace_bytes": (ctypes.c_size_t, []),
     "mmt_rgbd_assemble": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _I, _P, _P, ctypes.c_int64, _P,
                                ctypes.c_size_t, _P]),

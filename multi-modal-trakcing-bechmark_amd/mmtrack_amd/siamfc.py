@@ -9,6 +9,10 @@ algorithm and DESIGN.md §8). Per frame, on the GPU:
 
 GOT-10k-style tracker interface: ``init(img, box)``, ``update(img) -> box``, ``track(frames, box)``.
 No CPU path: frames go to the device and every op raises without the HIP library.
+
+``SiamFCPool`` runs many sequences per launch with the tracker state in device memory (the windows are formed
+and the state advanced by the kernels; the host reads one record per sequence and frame, one frame behind);
+``TrackerSiamFC`` is the sequential path and the yardstick of the pool's tests.
 """
 from __future__ import annotations
 
@@ -80,21 +84,31 @@ class AlexNetV1:
             cin_pitch = ldy
         self.out_channels = self.layers[-1]["ldy"]
         self._bufs = {}
+        self._alloc = {}   # (H, W) -> (images allocated, their buffers)
+
+    def reserve(self, n, H, W):
+        """Allocate the activations of n images of H x W once: every call with fewer images of that size then
+        runs in the first rows of these buffers (a pool at capacity serves any smaller launch)."""
+        if self._alloc.get((H, W), (0, None))[0] >= n:
+            return
+        bufs, h, w = [], H, W
+        for L in self.layers:
+            h = (h - L["kh"]) // L["stride"] + 1
+            w = (w - L["kw"]) // L["stride"] + 1
+            y = torch.empty(n, h, w, L["ldy"], device=self.device)
+            p = None
+            if L["pool"]:
+                h, w = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+                p = torch.empty(n, h, w, L["ldy"], device=self.device)
+            bufs.append((y, p))
+        self._alloc[(H, W)] = (n, bufs)
+        self._bufs = {k: v for k, v in self._bufs.items() if k[1:] != (H, W)}   # views of the buffers replaced
 
     def _buffers(self, n, H, W):
         key = (n, H, W)
         if key not in self._bufs:
-            bufs = []
-            for L in self.layers:
-                H = (H - L["kh"]) // L["stride"] + 1
-                W = (W - L["kw"]) // L["stride"] + 1
-                y = torch.empty(n, H, W, L["ldy"], device=self.device)
-                p = None
-                if L["pool"]:
-                    H, W = (H - 3) // 2 + 1, (W - 3) // 2 + 1
-                    p = torch.empty(n, H, W, L["ldy"], device=self.device)
-                bufs.append((y, p))
-            self._bufs[key] = bufs
+            self.reserve(n, H, W)
+            self._bufs[key] = [(y[:n], None if p is None else p[:n]) for y, p in self._alloc[(H, W)][1]]
         return self._bufs[key]
 
     def __call__(self, x, stream):
@@ -238,3 +252,312 @@ class TrackerSiamFC:
                 boxes[f, :] = self.update(img)
             times[f] = time.time() - begin
         return boxes, times
+
+
+def plan_slots(lengths, capacity):
+    """The slot bookkeeping of ``SiamFCPool.track_sequences`` (pure: no GPU).  ``lengths[i] >= 2`` frames of
+    sequence i (frame 0 initialises, frames 1.. are tracked), ``capacity`` slots.  Returns the steps, each a dict
+
+      inits  [(slot, seq)]  sequences initialised from their frame 0 before this step's launch
+      moves  [(src, dst)]   slots re-homed first (``SiamFCPool.move``): a finished sequence's slot below the new
+                            count is taken by the next pending sequence, or else by the active slot at the top
+      track  [(seq, frame)] the launch: slot k tracks frame ``frame`` of sequence ``seq``, for k in [0, n)
+
+    so the active slots are always [0, n), a move only comes from a slot >= the new count, sequences start in
+    the order given and every sequence sees each of its frames exactly once."""
+    if capacity < 1 or any(L < 2 for L in lengths):
+        raise ValueError("plan_slots: capacity >= 1 and every sequence at least 2 frames")
+    nxt = [0] * len(lengths)
+    pending = list(range(len(lengths)))
+    slots, steps = [], []
+    while True:
+        slots = [s if s is not None and nxt[s] < lengths[s] else None for s in slots]
+        inits, moves = [], []
+        for k in range(capacity):
+            if not pending:
+                break
+            if k == len(slots):
+                slots.append(None)
+            if slots[k] is None:
+                slots[k] = pending.pop(0)
+                nxt[slots[k]] = 1
+                inits.append((k, slots[k]))
+        count = sum(s is not None for s in slots)
+        for dst in range(count):
+            if slots[dst] is None:
+                src = max(k for k, s in enumerate(slots) if s is not None)
+                moves.append((src, dst))
+                slots[dst], slots[src] = slots[src], None
+        slots = slots[:count]
+        if not count:
+            return steps
+        steps.append(dict(inits=inits, moves=moves, track=[(s, nxt[s]) for s in slots]))
+        for s in slots:
+            nxt[s] += 1
+
+
+class SiamFCPool:
+    """``capacity`` SiamFC sequences with their tracker state on the device, n of them advanced per launch
+    sequence: mmt_siamfc_pool_crop (windows from the states) -> one AlexNetV1 pass over n * scale_num crops ->
+    mmt_xcorr_nhwc_group -> mmt_siamfc_pool_update (selection, state law, result records into pinned host
+    memory).  13 launches per frame for any n, nothing read back before the next frame is launched.  Every stage
+    is the sequential tracker's device code, so the boxes are ``TrackerSiamFC``'s for any n and any slot."""
+
+    def __init__(self, state_dict=None, capacity=1, device=None, net_path=None, **cfg):
+        self.lib = _lib.load()
+        if not torch.cuda.is_available():
+            raise RuntimeError("SiamFCPool needs an MI355X (HIP device); there is no CPU path")
+        if isinstance(state_dict, (str, bytes)) or hasattr(state_dict, "__fspath__"):
+            net_path, state_dict = state_dict, None
+        if capacity < 1:
+            raise ValueError("capacity must be at least 1")
+        self.device = dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self.cfg = c = dict(CFG, **cfg)
+        if state_dict is None:
+            state_dict = torch.load(net_path, map_location="cpu", weights_only=True)
+        state_dict = {k[len("module."):] if k.startswith("module.") else k: v for k, v in state_dict.items()}
+        self.capacity = cap = int(capacity)
+        self.scale_num = S = c["scale_num"]
+        if not 1 <= S <= 8:
+            raise ValueError("scale_num must be 1..8")
+        self.backbone = AlexNetV1(state_dict, dev)
+        self.backbone.reserve(cap * S, c["instance_sz"], c["instance_sz"])
+        self.upscale_sz = up = c["response_up"] * c["response_sz"]
+        h = np.hanning(up)
+        self.hann1d = torch.from_numpy(h).to(dev)
+        self.scale_factors = c["scale_step"] ** np.linspace(-(S // 2), S // 2, S)
+        self.params = self._params(c["instance_sz"], self.scale_factors, float(np.outer(h, h).sum()))
+        # the exemplar crop of init(): one window of side round(z_sz) -- the init state carries z_sz as its x_sz
+        self.zparams = self._params(c["exemplar_sz"], [1.0], self.params.hann_sum)
+        self.sbytes, self.rbytes = ctypes.sizeof(_lib.MmtSiamfcState), ctypes.sizeof(_lib.MmtSiamfcResult)
+        self.fbytes = ctypes.sizeof(_lib.MmtDimpFrame)
+        self.states = torch.zeros((cap + 1) * self.sbytes, dtype=torch.uint8, device=dev)   # [cap]: init()'s scratch
+        self.zbuf = torch.zeros(1, c["exemplar_sz"], c["exemplar_sz"], 3, device=dev)
+        fz = self.backbone(self.zbuf, self._stream())   # its shape (the buffers of n = 1 exist from here on)
+        self.exemplars = torch.zeros((cap,) + tuple(fz.shape[1:]), device=dev)
+        self.xbuf = torch.empty(cap * S, c["instance_sz"], c["instance_sz"], 3, device=dev)
+        self.resp = torch.empty(cap * S, c["response_sz"], c["response_sz"], device=dev)
+        self.scratch = torch.empty(cap * S * up * up, device=dev)
+        self.results = torch.zeros(cap * self.rbytes, dtype=torch.uint8, device=dev)
+        self.init_desc = torch.zeros(self.fbytes, dtype=torch.uint8, device=dev)
+        self._host_ptrs = []
+        # frame descriptors and result records in mapped pinned memory the kernels read / write in place; two
+        # parities, so frame k + 1 is launched before frame k's records are read
+        self.desc_host = [self._host_buffer(cap * self.fbytes) for _ in range(2)]
+        self.res_host = [self._host_buffer(cap * self.rbytes) for _ in range(2)]
+        self._stage = {}                 # (slot, parity) -> pinned staging of a host frame
+        self._launch_ev = [None, None]   # per parity: the event behind its last launch
+        self._unfetched = [False, False]
+        self._parity = 0
+
+    # ------------------------------------------------------------------ plumbing
+    def _params(self, out_sz, factors, hann_sum):
+        c, p = self.cfg, _lib.MmtSiamfcParams()
+        p.scale_num, p.instance_sz, p.response_sz = len(factors), out_sz, c["response_sz"]
+        p.response_up, p.total_stride, p.scale_penalty = c["response_up"], c["total_stride"], c["scale_penalty"]
+        for i, f in enumerate(factors):
+            p.scale_factors[i] = float(f)
+        p.scale_lr, p.window_influence, p.hann_sum = c["scale_lr"], c["window_influence"], hann_sum
+        return p
+
+    def _host_buffer(self, nbytes):
+        ptr = self.lib.mmt_host_alloc(nbytes)
+        if not ptr:
+            raise RuntimeError("mmt_host_alloc failed")
+        self._host_ptrs.append(ptr)
+        return torch.frombuffer((ctypes.c_uint8 * nbytes).from_address(ptr), dtype=torch.uint8)
+
+    def __del__(self):
+        for p in getattr(self, "_host_ptrs", []):
+            try:
+                self.lib.mmt_host_free(p)
+            except Exception:
+                pass
+        self._host_ptrs = []
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _state_ptr(self, slot):
+        return ctypes.c_void_p(self.states.data_ptr() + slot * self.sbytes)
+
+    def _check_slots(self, first, n):
+        if n < 1 or first < 0 or first + n > self.capacity:
+            raise ValueError(f"slots [{first}, {first + n}) outside the pool's {self.capacity}")
+
+    def _device_frame(self, image, key=None):
+        """A frame the kernels can index: device tensors in place, host frames through pinned staging `key`
+        (None: a blocking copy) and an asynchronous copy."""
+        t = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] < 3:
+            raise ValueError("frame must be H x W x C uint8 with C >= 3")
+        if t.is_cuda:
+            t = t.to(self.device)
+            ok = t.stride(2) == 1 and t.stride(1) == t.shape[2] and t.stride(0) >= t.shape[1] * t.shape[2]
+            return t if ok else t.contiguous()
+        if key is None:
+            return t.contiguous().to(self.device)
+        st = self._stage.get(key)
+        if st is None or st.shape != t.shape:
+            st = self._stage[key] = torch.empty(t.shape, dtype=torch.uint8, pin_memory=True)
+        st.copy_(t)
+        return st.to(self.device, non_blocking=True)
+
+    @staticmethod
+    def _describe(d, f):
+        d.data, d.stride, d.H, d.W, d.C = f.data_ptr(), f.stride(0), f.shape[0], f.shape[1], f.shape[2]
+
+    def state(self, slot):
+        """The slot's device state, read back (synchronises): an ``MmtSiamfcState``."""
+        self._check_slots(slot, 1)
+        raw = self.states[slot * self.sbytes:(slot + 1) * self.sbytes].cpu().numpy().tobytes()
+        return _lib.MmtSiamfcState.from_buffer_copy(raw)
+
+    # ------------------------------------------------------------------ the tracker interface, per slot
+    @torch.no_grad()
+    def init(self, slot, img, box):
+        """``TrackerSiamFC.init`` for `slot`: its host arithmetic (float32 roundings included) gives the state, the
+        exemplar crop and the backbone run at n = 1 and the features go to the slot.  Stream-ordered: the border
+        colour is formed and stored on the device, nothing is read back."""
+        self._check_slots(slot, 1)
+        c, lib, s = self.cfg, self.lib, self._stream()
+        box = np.array([box[1] - 1 + (box[3] - 1) / 2, box[0] - 1 + (box[2] - 1) / 2, box[3], box[2]],
+                       dtype=np.float32)
+        center, target_sz = box[:2], box[2:]
+        context = c["context"] * np.sum(target_sz)
+        z_sz = np.sqrt(np.prod(target_sz + context))
+        x_sz = z_sz * c["instance_sz"] / c["exemplar_sz"]
+        frame = self._device_frame(img)
+        avg = frame[..., :3].double().mean(dim=(0, 1))
+        pad = torch.clamp(torch.round(avg), 0, 255).to(torch.int32)   # half to even, as np.rint
+        st = _lib.MmtSiamfcState()
+        st.center[0], st.center[1] = float(center[0]), float(center[1])
+        st.target_sz[0], st.target_sz[1] = float(target_sz[0]), float(target_sz[1])
+        st.z_sz, st.x_sz, st.frame_num = float(z_sz), float(x_sz), 0
+        zst = _lib.MmtSiamfcState.from_buffer_copy(bytes(st))
+        zst.x_sz = float(z_sz)
+        raw = torch.frombuffer(bytearray(bytes(st) + bytes(zst)), dtype=torch.uint8).to(self.device)
+        sb = self.sbytes
+        self.states[slot * sb:(slot + 1) * sb].copy_(raw[:sb])
+        self.states[self.capacity * sb:].copy_(raw[sb:])
+        po = _lib.MmtSiamfcState.pad.offset
+        for k in (slot, self.capacity):
+            self.states[k * sb + po:k * sb + po + 12].view(torch.int32).copy_(pad)
+        d = _lib.MmtDimpFrame()
+        self._describe(d, frame)
+        self.init_desc.copy_(torch.frombuffer(bytearray(bytes(d)), dtype=torch.uint8))
+        _rc(lib.mmt_siamfc_pool_crop(self._state_ptr(self.capacity), ctypes.c_void_p(self.init_desc.data_ptr()), 1,
+                                     ctypes.byref(self.zparams), ctypes.c_void_p(self.zbuf.data_ptr()), None, s),
+            "mmt_siamfc_pool_crop")
+        self.exemplars[slot].copy_(self.backbone(self.zbuf, s)[0])
+
+    @torch.no_grad()
+    def submit(self, frames, first=0):
+        """Launch one frame for slots first .. first + len(frames) - 1; returns the ticket ``fetch`` takes.  One
+        earlier ticket may still be unfetched."""
+        n = len(frames)
+        self._check_slots(first, n)
+        buf = self._parity
+        if self._unfetched[buf]:
+            raise RuntimeError("SiamFCPool: two submitted frames are unfetched; fetch the older one first")
+        if self._launch_ev[buf] is not None:
+            self._launch_ev[buf].synchronize()   # this parity's descriptors / staging were read by that launch
+        c, lib, s, S = self.cfg, self.lib, self._stream(), self.scale_num
+        fr = [self._device_frame(f, (first + i, buf)) for i, f in enumerate(frames)]
+        desc_ptr = self.desc_host[buf].data_ptr() + first * self.fbytes
+        desc = (_lib.MmtDimpFrame * n).from_address(desc_ptr)
+        for i, f in enumerate(fr):
+            self._describe(desc[i], f)
+        x = self.xbuf[:n * S]
+        _rc(lib.mmt_siamfc_pool_crop(self._state_ptr(first), ctypes.c_void_p(desc_ptr), n, ctypes.byref(self.params),
+                                     ctypes.c_void_p(x.data_ptr()), None, s), "mmt_siamfc_pool_crop")
+        fx = self.backbone(x, s)
+        z = self.exemplars[first]
+        _rc(lib.mmt_xcorr_nhwc_group(ctypes.c_void_p(z.data_ptr()), z.numel(), S, ctypes.c_void_p(fx.data_ptr()),
+                                     ctypes.c_void_p(self.resp.data_ptr()), n * S, fx.shape[3], z.shape[0], z.shape[1],
+                                     fx.shape[1], fx.shape[2], ctypes.c_float(c["out_scale"]), ctypes.c_float(0.0), s),
+            "mmt_xcorr_nhwc_group")
+        _rc(lib.mmt_siamfc_pool_update(ctypes.c_void_p(self.resp.data_ptr()), n, ctypes.byref(self.params),
+                                       ctypes.c_void_p(self.hann1d.data_ptr()), ctypes.c_void_p(self.scratch.data_ptr()),
+                                       self._state_ptr(first), ctypes.c_void_p(self.results.data_ptr() + first * self.rbytes),
+                                       ctypes.c_void_p(self.res_host[buf].data_ptr() + first * self.rbytes), s),
+            "mmt_siamfc_pool_update")
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._launch_ev[buf] = ev
+        self._unfetched[buf] = True
+        self._parity = buf ^ 1
+        return ev, buf, first, n, fr   # fr: the frames stay alive until their launch has been waited for
+
+    def fetch(self, ticket):
+        """Wait for a submitted frame: (boxes [n, 4] float64 as ``TrackerSiamFC.update`` returns them, values [n],
+        errs [n]; err 1: a degenerate window, that sequence kept its state)."""
+        ev, buf, first, n, _ = ticket
+        ev.synchronize()
+        self._unfetched[buf] = False
+        rec = (_lib.MmtSiamfcResult * n).from_address(self.res_host[buf].data_ptr() + first * self.rbytes)
+        boxes = np.array([list(r.box) for r in rec], dtype=np.float64).reshape(n, 4)
+        values = np.array([r.value for r in rec], dtype=np.float32)
+        errs = np.array([r.err for r in rec], dtype=np.int32)
+        self.last_selection = [(r.scale_id, r.row, r.col) for r in rec]
+        return boxes, values, errs
+
+    def update(self, frames, first=0):
+        return self.fetch(self.submit(frames, first))
+
+    @torch.no_grad()
+    def move(self, src, dst):
+        """Re-home slot `src` to `dst`: its state and exemplar, device to device, stream-ordered."""
+        self._check_slots(src, 1)
+        self._check_slots(dst, 1)
+        if src == dst:
+            return
+        sb = self.sbytes
+        self.states[dst * sb:(dst + 1) * sb].copy_(self.states[src * sb:(src + 1) * sb])
+        self.exemplars[dst].copy_(self.exemplars[src])
+
+    # ------------------------------------------------------------------ a dataset
+    def track_sequences(self, seqs, on_done=None):
+        """seqs: [(name, frames, init_box)] of any lengths.  Tracks them `capacity` at a time (plan_slots: active
+        slots contiguous, a finished sequence's slot taken by the next pending one) with one frame of latency
+        between launch and read-back.  Returns, per sequence, ``(boxes, times)`` as ``TrackerSiamFC.track``
+        (times: the sequence's share of each launch's wall time); ``on_done(name, boxes, times)`` is called as
+        each sequence finishes."""
+        out = []
+        for name, frames, box in seqs:
+            boxes = np.zeros((len(frames), 4))
+            if len(frames):
+                boxes[0] = box
+            out.append((boxes, np.zeros(len(frames))))
+        live = [i for i, (_, frames, _) in enumerate(seqs) if len(frames) >= 2]
+        for i in range(len(seqs)):
+            if i not in live and on_done is not None:
+                on_done(seqs[i][0], *out[i])
+        steps = plan_slots([len(seqs[i][1]) for i in live], self.capacity)
+
+        def finish(pend):
+            ticket, track, t0 = pend
+            boxes, _, _ = self.fetch(ticket)
+            dt = (time.time() - t0) / len(track)
+            for k, (s, f) in enumerate(track):
+                i = live[s]
+                out[i][0][f] = boxes[k]
+                out[i][1][f] = dt
+                if f == len(seqs[i][1]) - 1 and on_done is not None:
+                    on_done(seqs[i][0], *out[i])
+
+        pend = None
+        for st in steps:
+            t0 = time.time()
+            for src, dst in st["moves"]:
+                self.move(src, dst)
+            for slot, s in st["inits"]:
+                _, frames, box = seqs[live[s]]
+                self.init(slot, frames[0], box)
+            ticket = self.submit([seqs[live[s]][1][f] for s, f in st["track"]], 0)
+            if pend is not None:
+                finish(pend)
+            pend = (ticket, st["track"], t0)
+        if pend is not None:
+            finish(pend)
+        return out
