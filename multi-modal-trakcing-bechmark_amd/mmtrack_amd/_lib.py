@@ -356,3 +356,22 @@ def load():
                           f"MMT_ABI_VERSION); rebuild it")
     _lib = lib
     return lib
+
+
+def rc(code, what):
+    """Raise for a failed library call: ValueError for MMT_E_ARG, RuntimeError for the rest."""
+    if code == MMT_E_ARG:
+        raise ValueError(f"{what}: invalid argument")
+    if code != MMT_OK:
+        raise RuntimeError(f"{what} failed ({code})")
+
+
+def ptr(t):
+    """A tensor's device address as a pointer argument (None: a null pointer)."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def stream(dev):
+    """The current torch stream of dev as a hipStream_t argument."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)

@@ -13,6 +13,7 @@ import math
 import torch
 
 from . import _lib
+from ._lib import rc as _rc, stream as _stream
 
 
 def _check(t, name, dims):
@@ -21,17 +22,6 @@ def _check(t, name, dims):
     if t.dim() != dims:
         raise ValueError(f"{name} must have {dims} dims, got {tuple(t.shape)}")
     return t.contiguous()
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _rc(rc, what):
-    if rc == -1:
-        raise ValueError(f"{what}: invalid argument")
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc})")
 
 
 def apply_filter(feat, filter):

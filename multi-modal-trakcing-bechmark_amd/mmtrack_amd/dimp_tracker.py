@@ -442,7 +442,7 @@ class DimpPool:
             d.data, d.stride, d.H, d.W, d.C = f.data_ptr(), f.stride(0), f.shape[0], f.shape[1], f.shape[2]
         sz = [int(v) for v in self.tparams.img_sample_sz]
         C = fr[0].shape[2]
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        stream = _lib.stream(self.dev)
         if net.precision == "f16x3" and C == 6 and FUSED_SAMPLE:
             # the sampler writes the backbones' normalised 4-channel halves itself (same bits as sample + normalise)
             # (and clears the backbones' max words: no fill launch)

@@ -26,24 +26,17 @@ import ctypes
 import math
 import os
 
+from typing import NamedTuple
+
 import torch
 
 from . import _lib
+from .dimp_table import IMAGE, OUT, layer_table, reference_rows, row_work
 from .synth import RESNET50_LAYERS, dimp_shapes
 
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
-
-
-def _rc(rc, what):
-    if rc == -1:
-        raise ValueError(f"{what}: invalid argument")
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc})")
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+_rc, _p, _stream = _lib.rc, _lib.ptr, _lib.stream
 
 
 def range_scale(m):
@@ -101,9 +94,26 @@ class _Conv:
         """This conv's operands as one mmt_conv_group of an f16x3 launch (pool: the stem with the 3 x 3 / stride-2
         max-pool fused, MMT_CONV_POOL; out is then the pooled map)."""
         flags = (1 if relu else 0) | (2 if merge_max else 0) | (8 if pool else 0)
-        ptr = (lambda t: t.data_ptr() if t is not None else None)
-        return _lib.MmtConvGroup(x.data_ptr(), self.wh.data_ptr(), self.wl.data_ptr(), self.w_scale, ptr(self.b),
-                                 ptr(resid), out.data_ptr(), ptr(x_max), float(x_scale), ptr(y_max), flags)
+        return _group(self, x.data_ptr(), out.data_ptr(), flags, _addr(resid), _addr(x_max), x_scale, _addr(y_max))
+
+    def ws_need(self, lib, N, H, W, G, cin=None):
+        """The split-K workspace bytes an f16x3 launch of G groups asks for (0: no split)."""
+        return lib.mmt_conv2d_f16x3_ws_bytes(N, H, W, cin or self.cin, self.cout, self.kh, self.kw, self.stride,
+                                             self.pad, G)
+
+    def call(self, lib, groups, N, H, W, ws, need, cin=None):
+        """One mmt_conv2d_f16x3_groups launch over groups, prepared for _launch; ws: the workspace pointer."""
+        arr = (_lib.MmtConvGroup * len(groups))(*groups)
+        return lib.mmt_conv2d_f16x3_groups, "mmt_conv2d_f16x3_groups", (
+            arr, len(groups), N, H, W, cin or self.cin, self.kp, self.cout, self.kh, self.kw, self.stride, self.pad,
+            ws, need)
+
+    def call_f32(self, lib, x, N, H, W, out, relu=False, resid=None, merge_max=False):
+        """The mmt_conv2d_f32 launch on the pointers x, out and resid, prepared for _launch."""
+        flags = (1 if relu else 0) | (2 if merge_max else 0) | (4 if self.w4 else 0)
+        return lib.mmt_conv2d_f32, "mmt_conv2d_f32", (
+            x, N, H, W, self.cin, _p(self.w), _p(self.b), self.cout, self.kh, self.kw, self.stride, self.pad, resid,
+            out, flags)
 
     def __call__(self, lib, x, N, H, W, out, stream, relu=False, resid=None, merge_max=False, x_max=None,
                  x_scale=0.0, y_max=None, ws=None):
@@ -113,10 +123,8 @@ class _Conv:
         if self.f16x3:
             run_f16x3(lib, self, [self.group(x, out, relu, resid, merge_max, x_max, x_scale, y_max)], N, H, W, ws,
                       stream)
-            return out
-        flags = (1 if relu else 0) | (2 if merge_max else 0) | (4 if self.w4 else 0)
-        _rc(lib.mmt_conv2d_f32(_p(x), N, H, W, self.cin, _p(self.w), _p(self.b), self.cout, self.kh, self.kw,
-                               self.stride, self.pad, _p(resid), _p(out), flags, stream), "mmt_conv2d_f32")
+        else:
+            _launch(self.call_f32(lib, _p(x), N, H, W, _p(out), relu, _p(resid), merge_max), stream)
         return out
 
 
@@ -138,22 +146,28 @@ class _ConvDs:
         self.b = (c3.b.double() + ds.b.double()).float().to(dev)
 
     def group(self, x, out, relu=True, x_max=None, y_max=None):
-        ptr = (lambda t: t.data_ptr() if t is not None else None)
-        return _lib.MmtConvGroup(x.data_ptr(), self.wh.data_ptr(), self.wl.data_ptr(), self.w_scale, ptr(self.b),
-                                 None, out.data_ptr(), ptr(x_max), 0.0, ptr(y_max), 1 if relu else 0)
+        return _group(self, x.data_ptr(), out.data_ptr(), 1 if relu else 0, None, _addr(x_max), 0.0, _addr(y_max))
+
+    def ws_need(self, lib, N, H, W, G, cin=None):
+        """As _Conv.ws_need (cin: not used, the weights fix K)."""
+        return lib.mmt_conv2d_f16x3_ws_bytes(N, H, W, self.kp, self.cout, 1, 1, 1, 0, G)
+
+    def call(self, lib, groups, ds, N, H, W, H2, W2, ws, need):
+        """One mmt_conv2d_f16x3_ds_groups launch, prepared for _launch; ds: the addresses of (x2, its max words)
+        per backbone; ws: the workspace pointer."""
+        G = len(groups)
+        arr = (_lib.MmtConvGroup * G)(*groups)
+        darr = (_lib.MmtConvDs * G)(*[_lib.MmtConvDs(x2, x2m, 0.0) for x2, x2m in ds])
+        return lib.mmt_conv2d_f16x3_ds_groups, "mmt_conv2d_f16x3_ds_groups", (
+            arr, darr, G, N, H, W, self.cin3, H2, W2, self.cin_d, self.stride, self.kp, self.cout, ws, need)
 
     def run(self, lib, groups, ds, N, H, W, H2, W2, ws, stream):
         """groups: conv3's operands per backbone (x = conv2's output [N][H][W][Cin3]); ds: (x2 = the block input
         [N][H2][W2][Cin_d], its max words) per backbone."""
-        G = len(groups)
-        need = lib.mmt_conv2d_f16x3_ws_bytes(N, H, W, self.kp, self.cout, 1, 1, 1, 0, G)
+        need = self.ws_need(lib, N, H, W, len(groups))
         buf = ws(need) if (need and ws is not None) else None
-        arr = (_lib.MmtConvGroup * G)(*groups)
-        darr = (_lib.MmtConvDs * G)(*[_lib.MmtConvDs(x2.data_ptr(), x2m.data_ptr() if x2m is not None else None, 0.0)
-                                      for x2, x2m in ds])
-        _rc(lib.mmt_conv2d_f16x3_ds_groups(arr, darr, G, N, H, W, self.cin3, H2, W2, self.cin_d, self.stride, self.kp,
-                                           self.cout, _p(buf), need if buf is not None else 0, stream),
-            "mmt_conv2d_f16x3_ds_groups")
+        _launch(self.call(lib, groups, [(x2.data_ptr(), _addr(x2m)) for x2, x2m in ds], N, H, W, H2, W2, _p(buf),
+                          need if buf is not None else 0), stream)
 
 
 # f16x3: each stage's first Bottleneck runs conv3 + downsample as one GEMM (_ConvDs); MMT_DIMP_DSFUSE=0 (tuning A/B):
@@ -161,18 +175,38 @@ class _ConvDs:
 DS_FUSE = os.environ.get("MMT_DIMP_DSFUSE", "1") != "0"
 
 
+def _addr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _group(conv, x, y, flags, resid=None, x_max=None, x_scale=0.0, y_max=None):
+    """The weights of conv (a _Conv or a _ConvDs) and operands at device addresses as one mmt_conv_group."""
+    return _lib.MmtConvGroup(x, conv.wh.data_ptr(), conv.wl.data_ptr(), conv.w_scale, _addr(conv.b), resid, y, x_max,
+                             float(x_scale), y_max, flags)
+
+
+def _launch(call, stream):
+    """Run a prepared call (function, its name, its arguments but the stream) on stream."""
+    fn, what, args = call
+    _rc(fn(*args, stream), what)
+
+
 def run_f16x3(lib, conv, groups, N, H, W, ws, stream, cin=None):
     """One mmt_conv2d_f16x3_groups launch of conv's shape over groups (the twin layers of the two backbones, or
     one); split-K partials in ws(nbytes) when the library asks for a split.  cin=4: the stem over an image
     padded to 4 channels (mmt_image_normalize4)."""
-    G = len(groups)
-    cin = conv.cin if cin is None else cin
-    need = lib.mmt_conv2d_f16x3_ws_bytes(N, H, W, cin, conv.cout, conv.kh, conv.kw, conv.stride, conv.pad, G)
+    need = conv.ws_need(lib, N, H, W, len(groups), cin)
     buf = ws(need) if (need and ws is not None) else None
-    arr = (_lib.MmtConvGroup * G)(*groups)
-    _rc(lib.mmt_conv2d_f16x3_groups(arr, G, N, H, W, cin, conv.kp, conv.cout, conv.kh, conv.kw, conv.stride,
-                                    conv.pad, _p(buf), need if buf is not None else 0, stream),
-        "mmt_conv2d_f16x3_groups")
+    _launch(conv.call(lib, groups, N, H, W, _p(buf), need if buf is not None else 0, cin), stream)
+
+
+class _Plan(NamedTuple):
+    """The prepared launches of DiMPNet._backbones for one (N, H, W)."""
+    calls: list            # (function, its name, its arguments but the stream), in launch order
+    out_groups: list       # f16x3: the mmt_conv_group entries whose y is the returned layer3 map
+    out_ptr: ctypes.c_void_p   # fp32: the pointer argument of the launches that write it
+    out_max: object        # f16x3: the merged map's max words (slot 0)
+    out_shape: tuple
 
 
 class DiMPNet:
@@ -201,177 +235,120 @@ class DiMPNet:
 
         def bn(pre):
             return [sd[pre + s] for s in (".weight", ".bias", ".running_mean", ".running_var")]
-        self.backbones = []
+        self.convs = []   # per backbone: a dimp_table row's layer -> its _Conv ("<conv3>+ds": the fused _ConvDs)
         for fe in ("feature_extractor", "feature_extractor_depth"):
-            stem = _Conv(sd[fe + ".conv1.weight"], bn(fe + ".bn1"), stride=2, pad=3, dev=self.dev, f16x3=f16)
-            blocks = []
+            cv = {"stem": _Conv(sd[fe + ".conv1.weight"], bn(fe + ".bn1"), stride=2, pad=3, dev=self.dev, f16x3=f16)}
             for li, (planes, nb, stride) in enumerate(RESNET50_LAYERS):
                 for b in range(nb):
-                    pre = f"{fe}.layer{li + 1}.{b}"
-                    s = stride if b == 0 else 1
-                    c1 = _Conv(sd[pre + ".conv1.weight"], bn(pre + ".bn1"), dev=self.dev, f16x3=f16)
-                    c2 = _Conv(sd[pre + ".conv2.weight"], bn(pre + ".bn2"), stride=s, pad=1, dev=self.dev, f16x3=f16)
-                    c3 = _Conv(sd[pre + ".conv3.weight"], bn(pre + ".bn3"), dev=self.dev, f16x3=f16)
-                    ds = _Conv(sd[pre + ".downsample.0.weight"], bn(pre + ".downsample.1"), stride=s, dev=self.dev,
-                               f16x3=f16) if b == 0 else None
-                    blocks.append((c1, c2, c3, ds, _ConvDs(c3, ds, self.dev) if (f16 and ds is not None) else None))
-            self.backbones.append((stem, blocks))
+                    name = f"layer{li + 1}.{b}"
+                    pre, s = f"{fe}.{name}", stride if b == 0 else 1
+                    cv[name + ".conv1"] = _Conv(sd[pre + ".conv1.weight"], bn(pre + ".bn1"), dev=self.dev, f16x3=f16)
+                    cv[name + ".conv2"] = _Conv(sd[pre + ".conv2.weight"], bn(pre + ".bn2"), stride=s, pad=1,
+                                                dev=self.dev, f16x3=f16)
+                    c3 = cv[name + ".conv3"] = _Conv(sd[pre + ".conv3.weight"], bn(pre + ".bn3"), dev=self.dev,
+                                                     f16x3=f16)
+                    if b == 0:
+                        ds = cv[name + ".downsample"] = _Conv(sd[pre + ".downsample.0.weight"],
+                                                              bn(pre + ".downsample.1"), stride=s, dev=self.dev,
+                                                              f16x3=f16)
+                        if f16:
+                            cv[name + ".conv3+ds"] = _ConvDs(c3, ds, self.dev)
+            self.convs.append(cv)
         self.clf = _Conv(sd["classifier.feature_extractor.0.weight"], pad=1, dev=self.dev, f16x3=f16)
         self.fconv = _Conv(sd["classifier.filter_initializer.filter_conv.weight"], pad=1,
                            bias=sd["classifier.filter_initializer.filter_conv.bias"], dev=self.dev, f16x3=f16)
         # f16x3 activation range: sharded max|y| words per produced tensor, zeroed once per extract_backbone;
         # the normalised image and the InstanceL2Norm output have static bounds
         self._max_words = torch.zeros(128 * MAX_WORDS, dtype=torch.float32, device=self.dev) if f16 else None
-        self._nslot = 0
         self.image_scale = range_scale(max((1 - m) / s for m, s in zip(MEAN, STD)))
         self.l2_scale = lambda L: range_scale(self.norm_scale * math.sqrt(L))
         self._mean = (ctypes.c_float * 3)(*MEAN)
         self._std = (ctypes.c_float * 3)(*STD)
         self._bufs = {}
+        self._plans = {}   # (N, H, W, STEM_POOL, DS_FUSE) -> _Plan; emptied when a buffer is replaced
 
     # ------------------------------------------------------------------ helpers
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        return _stream(self.dev)
 
     def _buf(self, name, n):
         b = self._bufs.get(name)
         if b is None or b.numel() < n:
+            if b is not None:   # the plans hold the old buffer's address
+                self._plans.clear()
             b = self._bufs[name] = torch.empty(n, dtype=torch.float32, device=self.dev)
         return b[:n]
-
-    def _slot(self):
-        """The next tensor's sharded max words (f16x3), or None in fp32 mode."""
-        if self._max_words is None:
-            return None
-        k = self._nslot
-        self._nslot += 1
-        if (k + 1) * MAX_WORDS > self._max_words.numel():
-            raise RuntimeError("DiMPNet: out of max-word slots")
-        return self._max_words[k * MAX_WORDS:(k + 1) * MAX_WORDS]
 
     def _ws(self, nbytes):
         return self._buf("splitk", (nbytes + 3) // 4)
 
-    def _layer(self, convs, kws, N, H, W, s, cin=None):
-        """The same layer of each backbone: f16x3 runs the twins as one grouped launch (unless one merges into
-        the other's output); fp32 runs them in backbone order.  cin: the f16x3 input's channel count when it
-        differs from the conv's (4: the padded image)."""
-        if self.precision == "f16x3" and len(convs) > 1 and not any(kw.get("merge_max") for kw in kws):
-            run_f16x3(self.lib, convs[0], [c.group(**kw) for c, kw in zip(convs, kws)], N, H, W, self._ws, s, cin)
-            return
-        for c, kw in zip(convs, kws):
-            c(self.lib, kw.pop("x"), N, H, W, kw.pop("out"), s, ws=self._ws, **kw)
-
-    def _resnets(self, xs, N, H, W, out, s, out_max):
-        """Both ResNet-50s to layer3, layer by layer, of NHWC xs[k] [N, H, W, 3]; the RGB backbone writes out
-        [N, H/16, W/16, 1024] and the aux backbone's last conv max-merges into it (dimpnet.py:103).  f16x3: every
-        conv reads its input's max words and accumulates its output's (out_max for layer3, shared by the two
-        backbones so it bounds the merged map)."""
-        lib = self.lib
-        K = range(len(self.backbones))
-        stems = [bb[0] for bb in self.backbones]
-        h, w = stems[0].out_hw(H, W)
-        t0_max = [self._slot() for k in K]
-        f16 = self.precision == "f16x3"   # f16x3: the images come padded to 4 channels
-        H2, W2 = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-        cur = [self._buf(f"ping{k}", N * H2 * W2 * 256) for k in K]
-        if f16 and STEM_POOL:   # the max-pool fused into the stem: the full-resolution map is never written
-            self._layer(stems, [dict(x=xs[k], out=cur[k], relu=True, x_scale=self.image_scale, y_max=t0_max[k],
-                                     pool=True) for k in K], N, H, W, s, cin=4)
-        else:
-            t0 = [self._buf(f"stem{k}", N * h * w * 64) for k in K]
-            self._layer(stems, [dict(x=xs[k], out=t0[k], relu=True, x_scale=self.image_scale, y_max=t0_max[k])
-                                for k in K], N, H, W, s, cin=4 if f16 else None)
-            for k in K:
-                _rc(lib.mmt_maxpool2d_f32(_p(t0[k]), N, h, w, 64, 3, 2, 1, _p(cur[k]), s), "mmt_maxpool2d_f32")
-        cur_max = t0_max   # a max-pool never exceeds its input's maximum
-        H, W = H2, W2
-        nxt_name = "pong"
-        nblocks = len(self.backbones[0][1])
-        for i in range(nblocks):
-            c1s, c2s, c3s, dss, fus = zip(*[bb[1][i] for bb in self.backbones])
-            Ho, Wo = c2s[0].out_hw(H, W)
-            a = [self._buf(f"a{k}", N * H * W * c1s[0].cout) for k in K]
-            a_max = [self._slot() for k in K]
-            self._layer(c1s, [dict(x=cur[k], out=a[k], relu=True, x_max=cur_max[k], y_max=a_max[k]) for k in K],
-                        N, H, W, s)
-            b = [self._buf(f"b{k}", N * Ho * Wo * c2s[0].cout) for k in K]
-            b_max = [self._slot() for k in K]
-            self._layer(c2s, [dict(x=a[k], out=b[k], relu=True, x_max=a_max[k], y_max=b_max[k]) for k in K],
-                        N, H, W, s)
-            last = i == nblocks - 1
-            fused = fus[0] is not None and DS_FUSE and not last
-            if fused:   # conv3 + downsample in one GEMM: relu(conv3(b) + ds(cur) + b3 + b_d)
-                o = [self._buf(f"{nxt_name}{k}", N * Ho * Wo * c3s[0].cout) for k in K]
-                o_max = [self._slot() for k in K]
-                fus[0].run(lib, [fu.group(b[k], o[k], x_max=b_max[k], y_max=o_max[k]) for k, fu in zip(K, fus)],
-                           [(cur[k], cur_max[k]) for k in K], N, Ho, Wo, H, W, self._ws, s)
-                cur, cur_max, nxt_name = o, o_max, ("ping" if nxt_name == "pong" else "pong")
-                H, W = Ho, Wo
-                continue
-            if dss[0] is not None:
-                res = [self._buf(f"res{k}", N * Ho * Wo * dss[0].cout) for k in K]
-                # only ever a residual operand: no max words
-                self._layer(dss, [dict(x=cur[k], out=res[k], x_max=cur_max[k]) for k in K], N, H, W, s)
+    def _plan(self, N, H, W):
+        """The prepared launches of both ResNet-50s to layer3 on N images of H x W (dimp_table.layer_table with
+        this module's STEM_POOL / DS_FUSE): buffers at their final size, group arrays filled in, each launch's
+        split-K workspace asked of the library once.  The rows writing the merged layer3 map get its address per
+        forward pass (_backbones)."""
+        key = (N, H, W, STEM_POOL, DS_FUSE)
+        if key in self._plans:
+            return self._plans[key]
+        lib, f16, K = self.lib, self.precision == "f16x3", range(len(self.convs))
+        tab = layer_table(H, W, self.precision, STEM_POOL, DS_FUSE, len(K))
+        if f16 and tab.nslots * MAX_WORDS > self._max_words.numel():
+            raise RuntimeError("DiMPNet: out of max-word slots")
+        convs = [[self.convs[k].get(r.layer + ("+ds" if r.kind == "conv_ds" else "")) for k in r.backbones]
+                 for r in tab.rows]   # per row and backbone (a max-pool: None)
+        for r, cs in zip(tab.rows, convs):   # a launch takes its shape from the conv, its buffers' sizes from the row
+            for c in (cs if r.kind != "pool" else ()):
+                if r.kind == "conv_ds":
+                    same = (c.cout, c.cin3, c.cin_d, c.stride) == (r.cout, r.cin, r.x2_cin, r.x2_stride)
+                else:   # the f16x3 stem reads the image padded to 4 channels
+                    same = (c.cout, c.cin + (f16 and r.layer == "stem"), c.kh, c.kw, c.stride, c.pad) == \
+                        (r.cout, r.cin, r.k, r.k, r.stride, r.pad)
+                if not same:
+                    raise RuntimeError(f"DiMPNet: the weights of {r.layer} do not have the layer table's shape")
+        needs = [cs[0].ws_need(lib, N, r.H, r.W, len(cs), r.cin) if f16 and r.kind != "pool" else 0
+                 for r, cs in zip(tab.rows, convs)]
+        ws = _p(self._ws(max(needs))) if max(needs) else None
+        addr = {(name, k): self._buf(("xa", "xb")[k] if name == IMAGE else f"{name}{k}", N * n).data_ptr()
+                for name, n in tab.buffers.items() for k in K}
+        words = (lambda slot: self._max_words.data_ptr() + 4 * MAX_WORDS * slot if isinstance(slot, int) else None)
+        last = tab.rows[-1]
+        plan = _Plan([], [], ctypes.c_void_p(), self._max_words[:MAX_WORDS] if f16 else None,
+                     (N, last.Ho, last.Wo, last.cout))
+        for r, cs, need in zip(tab.rows, convs, needs):
+            at = (lambda name, i: addr.get((name, r.backbones[i])))   # None: no such operand, or OUT (set per pass)
+            if r.kind == "pool" or not f16:
+                x, resid = ctypes.c_void_p(at(r.x, 0)), ctypes.c_void_p(at(r.resid, 0))
+                y = plan.out_ptr if r.y == OUT else ctypes.c_void_p(at(r.y, 0))
+                call = (lib.mmt_maxpool2d_f32, "mmt_maxpool2d_f32", (x, N, r.H, r.W, r.cin, r.k, r.stride, r.pad, y)) \
+                    if r.kind == "pool" else cs[0].call_f32(lib, x, N, r.H, r.W, y, r.relu, resid, r.merge_max)
             else:
-                res = cur
-            if last:
-                o, o_max = [out] * len(K), [out_max] * len(K)
-                for k in K:   # the RGB map first, then the aux map merged into it
-                    self._layer([c3s[k]], [dict(x=b[k], out=out, relu=True, resid=res[k], merge_max=k > 0,
-                                                x_max=b_max[k], y_max=out_max)], N, Ho, Wo, s)
-            else:
-                o = [self._buf(f"{nxt_name}{k}", N * Ho * Wo * c3s[0].cout) for k in K]
-                o_max = [self._slot() for k in K]
-                self._layer(c3s, [dict(x=b[k], out=o[k], relu=True, resid=res[k], x_max=b_max[k], y_max=o_max[k])
-                                  for k in K], N, Ho, Wo, s)
-            cur, cur_max, nxt_name = o, o_max, ("ping" if nxt_name == "pong" else "pong")
-            H, W = Ho, Wo
-        return H, W
+                flags = (1 if r.relu else 0) | (2 if r.merge_max else 0) | (8 if r.pool else 0)
+                groups = [_group(c, at(r.x, i), at(r.y, i), flags, at(r.resid, i), words(r.x_slot[i]),
+                                 self.image_scale if r.x_slot[i] == IMAGE else 0.0, words(r.y_slot[i]))
+                          for i, c in enumerate(cs)]
+                if r.kind == "conv_ds":
+                    call = cs[0].call(lib, groups, [(at(r.x2, i), words(r.x2_slot[i])) for i in range(len(cs))], N, r.H,
+                                      r.W, r.x2_H, r.x2_W, ws if need else None, need)
+                else:
+                    call = cs[0].call(lib, groups, N, r.H, r.W, ws if need else None, need, r.cin)
+                if r.y == OUT:
+                    plan.out_groups.append(call[2][0][0])   # the group array's entry: a view, not a copy
+            plan.calls.append(call)
+        self._plans[key] = plan
+        return plan
 
     def flops(self, H=288, W=288):
         """Algorithmic FLOPs (2 x MACs) of extract_backbone + extract_classification_feat for one [6, H, W] image."""
-        total = 0
-        for stem, blocks in self.backbones:
-            h, w = stem.out_hw(H, W)
-            total += 2 * h * w * stem.cout * stem.kh * stem.kw * stem.cin
-            h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-            for c1, c2, c3, ds, _ in blocks:
-                ho, wo = c2.out_hw(h, w)
-                total += 2 * h * w * c1.cout * c1.cin
-                total += 2 * ho * wo * c2.cout * 9 * c2.cin
-                total += 2 * ho * wo * c3.cout * c3.cin
-                if ds is not None:
-                    total += 2 * ho * wo * ds.cout * ds.cin
-                h, w = ho, wo
-        return total + 2 * h * w * self.clf.cout * 9 * self.clf.cin
+        return sum(f for f, _ in self.layer_work(H, W))
 
     def layer_work(self, H=288, W=288):
         """(FLOPs, minimum HBM bytes) of every conv and max-pool of extract_backbone + the clf conv for one
-        [6, H, W] image: each layer's input read once, its output written once (and read back by the MAX merge),
-        the residual read, fp32 activations, f16x3 weights (hi + lo, read once per launch -- amortised over
-        the batch, so not counted per image).  The per-layer roofline of a batch is the sum over layers of
-        max(FLOPs / matrix peak, bytes / HBM bandwidth).  (The reference's layers as the yardstick: the fused
-        conv3 + downsample of the f16x3 path moves fewer bytes than the two layers it replaces.)"""
-        out = []
-        for bi, (stem, blocks) in enumerate(self.backbones):
-            h, w = stem.out_hw(H, W)
-            out.append((2 * h * w * stem.cout * stem.kh * stem.kw * stem.cin, 4 * (H * W * 3 + h * w * stem.cout)))
-            h2, w2 = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-            out.append((0, 4 * (h * w * 64 + h2 * w2 * 64)))   # max-pool
-            h, w, cin = h2, w2, 64
-            for k, (c1, c2, c3, ds, _) in enumerate(blocks):
-                ho, wo = c2.out_hw(h, w)
-                out.append((2 * h * w * c1.cout * c1.cin, 4 * (h * w * cin + h * w * c1.cout)))
-                out.append((2 * ho * wo * c2.cout * 9 * c2.cin, 4 * (h * w * c2.cin + ho * wo * c2.cout)))
-                merge = bi > 0 and k == len(blocks) - 1
-                out.append((2 * ho * wo * c3.cout * c3.cin,
-                            4 * (ho * wo * c3.cin + (3 if merge else 2) * ho * wo * c3.cout)))
-                if ds is not None:
-                    out.append((2 * ho * wo * ds.cout * ds.cin, 4 * (h * w * cin + ho * wo * ds.cout)))
-                h, w, cin = ho, wo, c3.cout
-        out.append((2 * h * w * self.clf.cout * 9 * self.clf.cin, 4 * (h * w * self.clf.cin + h * w * self.clf.cout)))
-        return out
+        [6, H, W] image (dimp_table.row_work: each layer's input read once, its output written once and read back
+        by the MAX merge, the residual read, fp32 activations; f16x3 weights (hi + lo) are read once per launch --
+        amortised over the batch, so not counted per image).  The per-layer roofline of a batch is the sum over
+        layers of max(FLOPs / matrix peak, bytes / HBM bandwidth).  (The reference's layers as the yardstick: the
+        fused conv3 + downsample of the f16x3 path moves fewer bytes than the two layers it replaces.)"""
+        return [row_work(r) for r in reference_rows(H, W, len(self.convs), self.clf.cout)]
 
     def roofline_ms(self, n, peak_tflops, hbm_tbps, H=288, W=288):
         """The per-layer roofline time (ms) of extract_backbone + clf conv over a batch of n images."""
@@ -392,7 +369,7 @@ class DiMPNet:
         xb = self._buf("xb", N * H * W * pc)
         norm = self.lib.mmt_image_normalize4 if f16 else self.lib.mmt_image_normalize
         _rc(norm(_p(im), N, 6, H, W, self._mean, self._std, _p(xa), _p(xb), s), "mmt_image_normalize")
-        return self._backbones(xa, xb, N, H, W, s)
+        return self._backbones(N, H, W, s)
 
     def norm4_buffers(self, N, H, W):
         """f16x3: the two normalised 4-channel NHWC halves [N*H*W*4] that extract_backbone_norm4 reads (a sampler
@@ -408,20 +385,24 @@ class DiMPNet:
     def extract_backbone_norm4(self, N, H, W, words_cleared=False):
         """extract_backbone on the patches already normalised into norm4_buffers(N, H, W); words_cleared: the
         max words were zeroed by an earlier launch on the stream (the normalising sampler)."""
-        xa, xb = self.norm4_buffers(N, H, W)
-        return self._backbones(xa, xb, N, H, W, self._stream(), words_cleared)
+        self.norm4_buffers(N, H, W)
+        return self._backbones(N, H, W, self._stream(), words_cleared)
 
-    def _backbones(self, xa, xb, N, H, W, s, words_cleared=False):
-        Hf, Wf = (H + 15) // 16, (W + 15) // 16
-        out = torch.empty(N, Hf, Wf, 1024, dtype=torch.float32, device=self.dev)
-        if self._max_words is not None:
-            if not words_cleared:
-                self._max_words.zero_()
-            self._nslot = 0
-        out_max = self._slot()
-        h, w = self._resnets([xa, xb], N, H, W, out, s, out_max)
-        assert (h, w) == (Hf, Wf)
-        self._layer3_max = (out, out_max)
+    def _backbones(self, N, H, W, s, words_cleared=False):
+        """Both ResNet-50s to layer3 on the normalised halves in the "xa" / "xb" buffers: the RGB backbone's last
+        conv writes the returned map [N, H/16, W/16, 1024], the aux backbone's max-merges into it (dimpnet.py:103).
+        f16x3: every conv reads its input's max words and accumulates its output's; slot 0, shared by the two last
+        convs, bounds the merged map."""
+        plan = self._plan(N, H, W)
+        out = torch.empty(plan.out_shape, dtype=torch.float32, device=self.dev)
+        if self._max_words is not None and not words_cleared:
+            self._max_words.zero_()
+        plan.out_ptr.value = out.data_ptr()   # fp32 launches
+        for g in plan.out_groups:             # f16x3 launches
+            g.y = out.data_ptr()
+        for call in plan.calls:
+            _launch(call, s)
+        self._layer3_max = (out, plan.out_max)
         return out
 
     def extract_classification_feat(self, layer3, nhwc=False):
@@ -470,7 +451,7 @@ def sample_patch_device(frame, geom, out_hw):
     out = torch.empty(1, C, int(out_hw[0]), int(out_hw[1]), dtype=torch.float32, device=frame.device)
     g = (ctypes.c_int * 7)(*[int(v) for v in geom])
     _rc(lib.mmt_sample_patch(_p(frame), H, W, C, frame.stride(0), g, int(out_hw[0]), int(out_hw[1]), _p(out),
-                             ctypes.c_void_p(torch.cuda.current_stream(frame.device).cuda_stream)), "mmt_sample_patch")
+                             _stream(frame.device)), "mmt_sample_patch")
     return out
 
 
@@ -481,7 +462,7 @@ def patch_transform_device(img, tf, out_hw):
     img = img.contiguous()
     out = torch.empty(1, C, int(out_hw[0]), int(out_hw[1]), dtype=torch.float32, device=img.device)
     _rc(lib.mmt_patch_transform(_p(img), C, Eh, Ew, ctypes.byref(tf), int(out_hw[0]), int(out_hw[1]), _p(out),
-                                ctypes.c_void_p(torch.cuda.current_stream(img.device).cuda_stream)),
+                                _stream(img.device)),
         "mmt_patch_transform")
     return out
 
@@ -505,7 +486,7 @@ def conv2d(x_nchw, w, bias=None, stride=1, pad=0, resid=None, relu=False, w4=Tru
         kw = dict(x_max=x_max, x_scale=0.0 if x_max is not None else range_scale(float(x.abs().max())), y_max=y_max)
         if split:
             kw["ws"] = lambda n: torch.empty((n + 3) // 4, dtype=torch.float32, device=x.device)
-    conv(lib, x, N, H, W, out, ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), relu=relu, resid=r,
+    conv(lib, x, N, H, W, out, _stream(x.device), relu=relu, resid=r,
          merge_max=merge_into is not None, **kw)
     return out.permute(0, 3, 1, 2)
 
@@ -518,7 +499,7 @@ def prroi_pool(feat_nchw, rois_xyxy, spatial_scale, ph, pw):
     out = torch.empty(N, C, ph, pw, dtype=torch.float32, device=f.device)
     r = torch.as_tensor(rois_xyxy, dtype=torch.float32).reshape(N, 4).to(f.device)
     _rc(lib.mmt_prroi_pool(_p(f), N, H, W, C, _p(r), spatial_scale, ph, pw, _p(out),
-                           ctypes.c_void_p(torch.cuda.current_stream(f.device).cuda_stream)), "mmt_prroi_pool")
+                           _stream(f.device)), "mmt_prroi_pool")
     return out
 
 

@@ -24,19 +24,13 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._lib import rc as _rc
 
 MMT_CONV_RELU, MMT_CONV_W4 = 1, 4   # include/mmtrack.h
 
 CFG = dict(out_scale=0.001, exemplar_sz=127, instance_sz=255, context=0.5, scale_num=3, scale_step=1.0375,
            scale_lr=0.59, scale_penalty=0.9745, window_influence=0.176, response_sz=17, response_up=16,
            total_stride=8)
-
-
-def _rc(rc, what):
-    if rc == -1:
-        raise ValueError(f"{what}: invalid argument")
-    if rc != 0:
-        raise RuntimeError(f"{what} failed ({rc})")
 
 
 class AlexNetV1:
@@ -161,7 +155,7 @@ class TrackerSiamFC:
         self.resp = torch.empty(n, 1, c["response_sz"], c["response_sz"], device=self.device)
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream(self.device)
 
     def _frame(self, img):
         if isinstance(img, torch.Tensor):
@@ -376,7 +370,7 @@ class SiamFCPool:
         self._host_ptrs = []
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream(self.device)
 
     def _state_ptr(self, slot):
         return ctypes.c_void_p(self.states.data_ptr() + slot * self.sbytes)

@@ -527,6 +527,28 @@ def test_dimpnet_matches_reference_golden(nets, precision):
 
 
 @pytest.mark.parametrize("precision", ["f16x3", "fp32"])
+def test_dimpnet_plans_survive_other_shapes(nets, precision):
+    """The cached launch plans: a batch run again after a smaller shape and a larger batch of its own size (which
+    replaces the buffers its plan was built on) gives its first bits -- layer3, clf features, f16x3 max words."""
+    net = nets[precision]
+    g = torch.Generator().manual_seed(11)
+    ims = {shp: (torch.rand(*shp, generator=g) * 255).cuda() for shp in ((3, 6, 75, 61), (1, 6, 33, 50), (4, 6, 75, 61))}
+
+    def run(shp):
+        l3 = net.extract_backbone(ims[shp])
+        words = net.max_words().clone() if precision == "f16x3" else None
+        return l3, net.extract_classification_feat(l3).clone(), words
+
+    first = run((3, 6, 75, 61))
+    assert first[0].shape == (3, 5, 4, 1024) and bool(first[0].abs().max() > 0)
+    runs = [run((3, 6, 75, 61)), run((1, 6, 33, 50)), run((4, 6, 75, 61)), run((3, 6, 75, 61))]
+    assert runs[0][0].data_ptr() != first[0].data_ptr()   # a fresh map per call: the first is still the caller's
+    for again in (runs[0], runs[3]):
+        for a, b in zip(first, again):
+            assert (a is None and b is None) or torch.equal(a, b)
+
+
+@pytest.mark.parametrize("precision", ["f16x3", "fp32"])
 def test_dimp_tracker_matches_reference_sequence(precision):
     """The reference DiMP tracker (DeT_DiMP50_Max parameters, use_iou_net False, torch.manual_seed before
     initialize) on a 24-frame synthetic RGB-D sequence: per-frame boxes IoU >= 0.999, identical
