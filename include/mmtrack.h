@@ -95,7 +95,9 @@ const char* mmt_version(void);
  * mmt_op_struct_layout.  9: mmt_op_gemm_ex, the GEMM launched as the engine launches it (groups, conv A, caller's
  * split-K workspace, deferred reduce), reporting the tile and K slices it ran.  10: the SiamFC tracker state
  * machine on the device (mmt_siamfc_pool_crop, mmt_xcorr_nhwc_group, mmt_siamfc_pool_update; mmt_op_struct_layout
- * 10 / 11 / 12 = mmt_siamfc_state / _params / _result). */
+ * 10 / 11 / 12 = mmt_siamfc_state / _params / _result).  The PrRoIPool ROI-list entries (mmt_prroi_pool_rois,
+ * _grad_rois, _grad_feat) joined revision 10 without a new number: they change no existing convention, and a
+ * binding that resolves every declared symbol at load rejects a library without them. */
 #define MMT_ABI_VERSION 10
 int mmt_abi_version(void);
 /* pinned host memory that kernels read and write in place (mapped + coherent: a kernel sees the host's latest
@@ -298,6 +300,29 @@ int mmt_instance_l2norm(const float* x, int N, int H, int W, int C, float scale,
  * feat NHWC, rois device [N][4] = x0, y0, x1, y1 (image coordinates) -> out [N][C][PH][PW]          */
 int mmt_prroi_pool(const float* feat, int N, int H, int W, int C, const float* rois, float spatial_scale, int PH,
                    int PW, float* out, void* hip_stream);
+/* PrRoIPool2D over any ROI list, with both gradients (csrc/prroi.hip; the filter initialiser keeps mmt_prroi_pool).
+ *   feat       fp32, channels last with channel stride 1; pix_pitch / row_pitch / img_pitch in floats, so an NHWC
+ *              buffer, a channel or column slice of a wider one, or a torch channels_last tensor is read in place
+ *   rois       device [K][5] = batch index, x0, y0, x1, y1 (image coordinates); any order, any number per image
+ *   out        [K][C][PH][PW];  grad_out likewise;  grad_rois [K][5] (column 0 = 0), every value written by one
+ *              workgroup in a fixed order;  grad_feat NHWC contiguous [N][H][W][C], every element written
+ * Asynchronous on hip_stream; no atomics, so two runs give the same bits.  Checked before any HIP call (MMT_E_ARG,
+ * nothing launched): null pointers; N, H, W, C, K < 1; C % 4; PH or PW outside 1..8; spatial_scale not finite or
+ * <= 0; pix_pitch < C, row_pitch < (W - 1) pix_pitch + C, img_pitch < (H - 1) row_pitch + (W - 1) pix_pitch + C; a
+ * pitch that is no multiple of 4 floats, or feat / out / grad_feat not 16-byte aligned (16-byte accesses along C).
+ * The ROI list is never read back, and the kernels tolerate anything in it: a ROI is valid when its five values are
+ * finite and 0 <= index < N (compared in float before the truncation to int); an invalid ROI, one whose scaled
+ * geometry overflows, and one with x1 <= x0 or y1 <= y0 give zero outputs and zero gradients; the cell loops are
+ * clamped to [-1, W - 1] x [-1, H - 1] (cells beyond add exact zeros), so no ROI value makes a thread read outside
+ * the map or visit more than (H + 1)(W + 1) cells per bin.                                                    */
+int mmt_prroi_pool_rois(const float* feat, int N, int H, int W, int C, int64_t pix_pitch, int64_t row_pitch,
+                        int64_t img_pitch, const float* rois, int K, float spatial_scale, int PH, int PW, float* out,
+                        void* hip_stream);
+int mmt_prroi_pool_rois_grad_rois(const float* feat, int N, int H, int W, int C, int64_t pix_pitch, int64_t row_pitch,
+                                  int64_t img_pitch, const float* rois, int K, float spatial_scale, int PH, int PW,
+                                  const float* out, const float* grad_out, float* grad_rois, void* hip_stream);
+int mmt_prroi_pool_rois_grad_feat(int N, int H, int W, int C, const float* rois, int K, float spatial_scale, int PH,
+                                  int PW, const float* grad_out, float* grad_feat, void* hip_stream);
 /* sample_patch (pytracking/features/preprocessing.py:49-125) from an H x W x C uint8 device frame:
  * geom = {df, os_y, os_x, tl_y, tl_x, sz_h, sz_w} (pre-downsample factor and offset, crop top-left and
  * size in the downsampled image, replicate padding) -> bilinear resize -> float NCHW [C][out_h][out_w] */

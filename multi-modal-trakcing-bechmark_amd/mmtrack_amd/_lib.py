@@ -285,6 +285,9 @@ SIGNATURES = {
     "mmt_instance_l2norm_ws_bytes": (ctypes.c_size_t, [_I, _I, _I]),
     "mmt_instance_l2norm": (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
     "mmt_prroi_pool": (_I, [_P, _I, _I, _I, _I, _P, _F, _I, _I, _P, _P]),
+    "mmt_prroi_pool_rois": (_I, [_P, _I, _I, _I, _I, _I64, _I64, _I64, _P, _I, _F, _I, _I, _P, _P]),
+    "mmt_prroi_pool_rois_grad_rois": (_I, [_P, _I, _I, _I, _I, _I64, _I64, _I64, _P, _I, _F, _I, _I, _P, _P, _P, _P]),
+    "mmt_prroi_pool_rois_grad_feat": (_I, [_I, _I, _I, _I, _P, _I, _F, _I, _I, _P, _P, _P]),
     "mmt_sample_patch": (_I, [_P, _I, _I, _I, ctypes.c_int64, _P, _I, _I, _P, _P]),
     "mmt_patch_transform": (_I, [_P, _I, _I, _I, ctypes.POINTER(MmtPatchTf), _I, _I, _P, _P]),
     "mmt_rgbx_merge": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _I, _P, ctypes.c_int64, _P]),
