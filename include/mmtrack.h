@@ -97,7 +97,8 @@ const char* mmt_version(void);
  * machine on the device (mmt_siamfc_pool_crop, mmt_xcorr_nhwc_group, mmt_siamfc_pool_update; mmt_op_struct_layout
  * 10 / 11 / 12 = mmt_siamfc_state / _params / _result).  The PrRoIPool ROI-list entries (mmt_prroi_pool_rois,
  * _grad_rois, _grad_feat) joined revision 10 without a new number: they change no existing convention, and a
- * binding that resolves every declared symbol at load rejects a library without them. */
+ * binding that resolves every declared symbol at load rejects a library without them; the IoU-Net predictor entries
+ * (mmt_iounet_*; mmt_op_struct_layout 13 / 14 / 15 = mmt_iounet_head / _map / _feat) likewise. */
 #define MMT_ABI_VERSION 10
 int mmt_abi_version(void);
 /* pinned host memory that kernels read and write in place (mapped + coherent: a kernel sees the host's latest
@@ -323,6 +324,58 @@ int mmt_prroi_pool_rois_grad_rois(const float* feat, int N, int H, int W, int C,
                                   const float* out, const float* grad_out, float* grad_rois, void* hip_stream);
 int mmt_prroi_pool_rois_grad_feat(int N, int H, int W, int C, const float* rois, int K, float spatial_scale, int PH,
                                   int PW, const float* grad_out, float* grad_feat, void* hip_stream);
+/* IoU-Net's predictor head and box ascent (csrc/iounet.hip; ltr/models/bbreg/atom_iou_net.py:96-136,
+ * pytracking/tracker/dimp/dimp.py:727-752).  fp32 throughout, products on the fp32 matrix cores, no atomics: two
+ * runs give the same bits, and a box's results do not depend on the other boxes or sequences of the call.
+ *
+ * mmt_iounet_linear: Y[rows][N] = act((X[rows][Kd] * scale) . W[N][Kd]^T + bias), the row-linear kernel on its own.
+ *   scale (nullable) [groups][Kd / bins]: row r is in group r / rows_per_group, column k in channel k / bins;
+ *   bias nullable; relu != 0: ReLU.  K is split into mmt_iounet_linear_ws_bytes(rows, Kd, N) / (rows N 4) slices,
+ *   a number that depends on Kd only; the partial sums live in ws and are added in slice order.
+ *   MMT_E_ARG before any HIP call: null X / W / Y / ws; rows, N < 1; Kd < 4 or Kd % 4; X, W or ws not 16-byte
+ *   aligned; ws_bytes too small; with scale: rows_per_group or bins < 1, Kd % bins.
+ * mmt_iounet_predict: boxes [B][P][4] (x, y, w, h in image coordinates) of B sequences -> iou [B][P]:
+ *   PrRoIPool 5 x 5 at 1/8 of l3 and 3 x 3 at 1/16 of l4 (mmt_prroi_pool_rois' conventions for the maps), each
+ *   pooled channel times the sequence's modulation mod3 [B][c3] / mod4 [B][c4], the two hidden layers
+ *   (w3 [n3][25 c3], w4 [n4][9 c4], BatchNorm folded, ReLU) and iou = wp . [h3, h4] + bp.  With grad_boxes
+ *   [B][P][4] also the gradient of sum(grad_iou * iou) to the boxes (grad_iou [B][P], null: ones).
+ * mmt_iounet_refine: iters times { predict with the gradient; box += step * grad * (w, h, w, h) with the pre-update
+ *   w, h; step *= step_decay }, step_pos for x, y and step_size for w, h, each product and sum rounded to fp32
+ *   in that order.  boxes_out [B][P][4] (may be boxes); iou [B][P] is the last forward's, i.e. of the boxes before
+ *   the last update, as the reference returns it.
+ *   MMT_E_ARG before any HIP call: null pointers (grad_iou and grad_boxes may be null); B, P < 1 or B P > 2^19;
+ *   c3, c4 not positive multiples of 4; n3, n4 not positive multiples of 16; w3, w4, a map, boxes, boxes_out,
+ *   grad_boxes or ws not 16-byte aligned; a map's H, W < 1 or pitches that mmt_prroi_pool_rois rejects; ws_bytes <
+ *   mmt_iounet_ws_bytes(B P, 25 c3, 9 c4, n3, n4); iters outside 1..1024; a step or bp not finite.
+ * No box value makes a kernel read outside a map: a box with a NaN, an infinity or a size <= 0 pools to zeros with
+ * zero gradient (PrRoIPool's rule), so its IoU is the head applied to zeros; other boxes are unaffected.
+ * The two _ws_bytes functions make no HIP call and return 0 for shapes the entries reject.                     */
+typedef struct mmt_iounet_head {
+  const float *w3, *b3, *w4, *b4; /* device: the folded hidden layers                                          */
+  const float* wp;                /* device [n3 + n4]: iou_predictor.weight                                    */
+  float bp;                       /* iou_predictor.bias                                                        */
+  int c3, c4, n3, n4;             /* pooled channels and hidden widths of the two levels                       */
+} mmt_iounet_head;
+typedef struct mmt_iounet_map {
+  const float* p; /* device, channels last, channel stride 1 */
+  int H, W;
+  int64_t pix, row, img; /* pitches in floats */
+} mmt_iounet_map;
+typedef struct mmt_iounet_feat {
+  int B; /* images = sequences */
+  int pad_;
+  mmt_iounet_map l3, l4; /* the IoU feature maps at 1/8 and 1/16 */
+} mmt_iounet_feat;
+size_t mmt_iounet_linear_ws_bytes(int rows, int Kd, int N);
+size_t mmt_iounet_ws_bytes(int rows, int Kd3, int Kd4, int N3, int N4);
+int mmt_iounet_linear(const float* X, int rows, int Kd, const float* W, int N, const float* bias, const float* scale,
+                      int rows_per_group, int bins, int relu, float* Y, void* ws, size_t ws_bytes, void* hip_stream);
+int mmt_iounet_predict(const mmt_iounet_head* head, const mmt_iounet_feat* feat, const float* mod3, const float* mod4,
+                       const float* boxes, int P, const float* grad_iou, float* iou, float* grad_boxes, void* ws,
+                       size_t ws_bytes, void* hip_stream);
+int mmt_iounet_refine(const mmt_iounet_head* head, const mmt_iounet_feat* feat, const float* mod3, const float* mod4,
+                      const float* boxes, int P, int iters, float step_pos, float step_size, float step_decay,
+                      float* boxes_out, float* iou, void* ws, size_t ws_bytes, void* hip_stream);
 /* sample_patch (pytracking/features/preprocessing.py:49-125) from an H x W x C uint8 device frame:
  * geom = {df, os_y, os_x, tl_y, tl_x, sz_h, sz_w} (pre-downsample factor and offset, crop top-left and
  * size in the downsampled image, replicate padding) -> bilinear resize -> float NCHW [C][out_h][out_w] */

@@ -393,6 +393,21 @@ int mmt_op_struct_layout(int which, size_t* out, int cap) {
       F(mmt_siamfc_result, box); F(mmt_siamfc_result, value); F(mmt_siamfc_result, scale_id); F(mmt_siamfc_result, row);
       F(mmt_siamfc_result, col); F(mmt_siamfc_result, err); F(mmt_siamfc_result, pad_);
       break;
+    case 13:
+      v.push_back(sizeof(mmt_iounet_head));
+      F(mmt_iounet_head, w3); F(mmt_iounet_head, b3); F(mmt_iounet_head, w4); F(mmt_iounet_head, b4);
+      F(mmt_iounet_head, wp); F(mmt_iounet_head, bp); F(mmt_iounet_head, c3); F(mmt_iounet_head, c4);
+      F(mmt_iounet_head, n3); F(mmt_iounet_head, n4);
+      break;
+    case 14:
+      v.push_back(sizeof(mmt_iounet_map));
+      F(mmt_iounet_map, p); F(mmt_iounet_map, H); F(mmt_iounet_map, W); F(mmt_iounet_map, pix);
+      F(mmt_iounet_map, row); F(mmt_iounet_map, img);
+      break;
+    case 15:
+      v.push_back(sizeof(mmt_iounet_feat));
+      F(mmt_iounet_feat, B); F(mmt_iounet_feat, pad_); F(mmt_iounet_feat, l3); F(mmt_iounet_feat, l4);
+      break;
     default:
       return 0;
   }

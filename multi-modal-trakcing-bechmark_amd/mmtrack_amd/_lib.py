@@ -224,9 +224,25 @@ class MmtSiamfcResult(ctypes.Structure):
                 ("row", ctypes.c_int), ("col", ctypes.c_int), ("err", ctypes.c_int), ("pad_", ctypes.c_int)]
 
 
+class MmtIounetHead(ctypes.Structure):
+    _fields_ = [("w3", ctypes.c_void_p), ("b3", ctypes.c_void_p), ("w4", ctypes.c_void_p), ("b4", ctypes.c_void_p),
+                ("wp", ctypes.c_void_p), ("bp", ctypes.c_float), ("c3", ctypes.c_int), ("c4", ctypes.c_int),
+                ("n3", ctypes.c_int), ("n4", ctypes.c_int)]
+
+
+class MmtIounetMap(ctypes.Structure):
+    _fields_ = [("p", ctypes.c_void_p), ("H", ctypes.c_int), ("W", ctypes.c_int), ("pix", ctypes.c_int64),
+                ("row", ctypes.c_int64), ("img", ctypes.c_int64)]
+
+
+class MmtIounetFeat(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int), ("pad_", ctypes.c_int), ("l3", MmtIounetMap), ("l4", MmtIounetMap)]
+
+
 # mmt_op_struct_layout's `which` of each mirror above
 STRUCT_LAYOUTS = [MmtCropParam, MmtSeqState, MmtTrackOut, MmtRingArgs, MmtCropArgs, MmtGeomArgs, MmtDecodeArgs,
-                  MmtGemmGroup, MmtGemmExArgs, MmtGemmRan, MmtSiamfcState, MmtSiamfcParams, MmtSiamfcResult]
+                  MmtGemmGroup, MmtGemmExArgs, MmtGemmRan, MmtSiamfcState, MmtSiamfcParams, MmtSiamfcResult,
+                  MmtIounetHead, MmtIounetMap, MmtIounetFeat]
 
 ABI_VERSION = 10   # include/mmtrack.h MMT_ABI_VERSION
 
@@ -288,6 +304,13 @@ SIGNATURES = {
     "mmt_prroi_pool_rois": (_I, [_P, _I, _I, _I, _I, _I64, _I64, _I64, _P, _I, _F, _I, _I, _P, _P]),
     "mmt_prroi_pool_rois_grad_rois": (_I, [_P, _I, _I, _I, _I, _I64, _I64, _I64, _P, _I, _F, _I, _I, _P, _P, _P, _P]),
     "mmt_prroi_pool_rois_grad_feat": (_I, [_I, _I, _I, _I, _P, _I, _F, _I, _I, _P, _P, _P]),
+    "mmt_iounet_linear_ws_bytes": (ctypes.c_size_t, [_I, _I, _I]),
+    "mmt_iounet_ws_bytes": (ctypes.c_size_t, [_I, _I, _I, _I, _I]),
+    "mmt_iounet_linear": (_I, [_P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, ctypes.c_size_t, _P]),
+    "mmt_iounet_predict": (_I, [ctypes.POINTER(MmtIounetHead), ctypes.POINTER(MmtIounetFeat), _P, _P, _P, _I, _P, _P,
+                                _P, _P, ctypes.c_size_t, _P]),
+    "mmt_iounet_refine": (_I, [ctypes.POINTER(MmtIounetHead), ctypes.POINTER(MmtIounetFeat), _P, _P, _P, _I, _I, _F, _F,
+                               _F, _P, _P, _P, ctypes.c_size_t, _P]),
     "mmt_sample_patch": (_I, [_P, _I, _I, _I, ctypes.c_int64, _P, _I, _I, _P, _P]),
     "mmt_patch_transform": (_I, [_P, _I, _I, _I, ctypes.POINTER(MmtPatchTf), _I, _I, _P, _P]),
     "mmt_rgbx_merge": (_I, [_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _I, _P, ctypes.c_int64, _P]),

@@ -420,3 +420,70 @@ def _calibrate_bn(sd, seed, size=96):
                 out = bn(conv(out, pre + ".conv3.weight"), pre + ".bn3")
                 res = bn(conv(x, pre + ".downsample.0.weight", s), pre + ".downsample.1") if b == 0 else x
                 x = F.relu(out + res)
+
+
+# ----------------------------------------------------------------------------- IoU-Net (AtomIoUNet, bb_regressor.*)
+def iounet_shapes(input_dim=(512, 1024), pred_input_dim=(256, 256), pred_inter_dim=(256, 256)):
+    """The AtomIoUNet state_dict keys without their prefix (ltr/models/bbreg/atom_iou_net.py:23-50): conv + BN + ReLU
+    blocks (Sequential: 0 = conv, 1 = BN), the two LinearBlocks and the IoU predictor.  DeT's dimp50 builds it with
+    input_dim (512, 1024), the plain dimp50 with (128, 256)."""
+    shp = OrderedDict()
+
+    def bn(pre, n):
+        for t in ("weight", "bias", "running_mean", "running_var"):
+            shp[f"{pre}.{t}"] = (n,)
+        shp[f"{pre}.num_batches_tracked"] = ()
+
+    def conv(name, cin, cout, k):
+        shp[f"{name}.0.weight"] = (cout, cin, k, k)
+        shp[f"{name}.0.bias"] = (cout,)
+        bn(f"{name}.1", cout)
+
+    conv("conv3_1r", input_dim[0], 128, 3)
+    conv("conv3_1t", input_dim[0], 256, 3)
+    conv("conv3_2t", 256, pred_input_dim[0], 3)
+    conv("fc3_1r", 128, 256, 3)
+    conv("conv4_1r", input_dim[1], 256, 3)
+    conv("conv4_1t", input_dim[1], 256, 3)
+    conv("conv4_2t", 256, pred_input_dim[1], 3)
+    conv("fc34_3r", 512, pred_input_dim[0], 1)
+    conv("fc34_4r", 512, pred_input_dim[1], 1)
+    for name, cin, cout, sz in (("fc3_rt", pred_input_dim[0], pred_inter_dim[0], 5),
+                                ("fc4_rt", pred_input_dim[1], pred_inter_dim[1], 3)):
+        shp[f"{name}.linear.weight"] = (cout, cin * sz * sz)
+        shp[f"{name}.linear.bias"] = (cout,)
+        bn(f"{name}.bn", cout)
+    shp["iou_predictor.weight"] = (1, pred_inter_dim[0] + pred_inter_dim[1])
+    shp["iou_predictor.bias"] = (1,)
+    return shp
+
+
+def make_iounet_state_dict(seed: int = 0, input_dim=(512, 1024), pred_input_dim=(256, 256), pred_inter_dim=(256, 256),
+                           prefix: str = "bb_regressor.", iou_gain: float = 12.0) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded fp32 AtomIoUNet weights under ``prefix``: He-normal (fan-in) convs and linears as the reference
+    initialises them (atom_iou_net.py:53-57), small random biases, and non-trivial BatchNorm statistics so the
+    host-side folding is exercised.  ``iou_predictor.weight`` is the He-normal draw times ``iou_gain``: a randomly
+    initialised predictor is nearly flat in the box (five ascent steps move a box by about a pixel), and the gain
+    makes the ascent move boxes by several pixels, so a wrong gradient shows (tests/test_iounet_ref.py pins that)."""
+    sd = OrderedDict()
+    for k, shp in iounet_shapes(input_dim, pred_input_dim, pred_inter_dim).items():
+        g = _gen(seed, "iounet." + k)
+        if k.endswith("num_batches_tracked"):
+            v = torch.tensor(0, dtype=torch.int64)
+        elif k.endswith("running_var"):
+            v = torch.rand(shp, generator=g) + 0.5
+        elif k.endswith("running_mean"):
+            v = torch.randn(shp, generator=g) * 0.1
+        elif ".1." in k or ".bn." in k:
+            v = torch.rand(shp, generator=g) * 0.6 + 0.4 if k.endswith("weight") else torch.randn(shp, generator=g) * 0.1
+        elif k.endswith(".bias"):
+            v = torch.randn(shp, generator=g) * 0.05
+        else:
+            fan_in = 1
+            for d in shp[1:]:
+                fan_in *= d
+            v = torch.randn(shp, generator=g) * math.sqrt(2.0 / fan_in)
+            if k == "iou_predictor.weight":
+                v = v * iou_gain
+        sd[prefix + k] = v.float().contiguous() if v.dtype != torch.int64 else v
+    return sd
